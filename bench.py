@@ -50,6 +50,19 @@ cpu_baseline: the reference's own ME (motion_estimation.c + its AVX2 kernels,
 compiled from the reference sources into oracle/_ref) on this host's cores
 (every CPU this process may use: affinity and cgroup quota), on a bounded
 sample of whole-picture passes of the same job, rank 0 at N = 1 only.
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does what `value` needs:
+it makes the pictures resident, warms up, times the N steps and prints the
+result line (value, ms_per_step, the pass's roofline from the timed steps' own
+events). Every other measurement above -- the per-kernel durations, overlapped,
+records_only, steady_state, upload, band_8k, cpu_baseline and the parity check
+against it -- takes runs of its own and is made only with --full, where the
+--no-* / --*-steps options select among them as before.
+
+--dump-outputs DIR writes what the last timed step left in its output buffer
+(the records and per-SB results of that step's pictures, which the workload's
+arguments fix: the synthetic sequence is the same in every run) as one .npy per
+field under DIR (dump_outputs below).
 """
 import argparse
 import ctypes as C
@@ -128,6 +141,13 @@ def main():
                     help="untimed steps first (the defaults are the driver's window; the GPU's clocks ramp over the "
                          "first ~25 ms of load, so this window runs ~10 %% below the steady state that "
                          "`steady_state` reports, DESIGN.md 4)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also every secondary measurement: per-kernel durations, overlapped, "
+                         "records_only, steady_state, upload, band_8k, cpu_baseline + parity (the options below "
+                         "that select among them apply only with --full); a plain run times the steps alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the output of the last timed step (records and per-SB results, one float .npy per "
+                         "field, at most 64 MB in all) under DIR")
     ap.add_argument("--steady-steps", type=int, default=200,
                     help="steps of the secondary steady-state measurement (after 300 more untimed steps, once the "
                          "clocks have ramped); 0 skips it")
@@ -167,6 +187,9 @@ def main():
     ap.add_argument("--shared-device", action="store_true",
                     help="every rank on HIP device 0 (rehearsal of the N > 1 path on a one-GPU box, with gloo)")
     args = ap.parse_args()
+    if not args.full:  # a plain run: the timed steps alone
+        args.kernel_samples = args.steady_steps = args.band_steps = 0
+        args.no_alt = args.no_records_only = args.no_upload = args.no_cpu_baseline = True
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -305,14 +328,19 @@ def main():
     fence()
     elapsed = time.perf_counter() - t0
     device_ms = ev0.elapsed_time(ev1) / args.steps  # the library stream's time per step (HIP events)
+    if args.dump_outputs:  # the last timed step's buffer, before any further leg rewrites it
+        dump_outputs(args.dump_outputs, S, local[(args.warmup + args.steps - 1) & 1].cpu().numpy(), P, chunk_bytes,
+                     rec_bytes, begin, count, R, with_sb, prefix=f"rank{rank}_" if world > 1 else "")
     # per-kernel durations: start/stop events attached to the stage dispatches
     # themselves (hipExtLaunchKernelGGL) over a sample of further steps
-    gpu.set_timing(True)
-    for i in range(args.kernel_samples):  # one lane, one launch per step: kernel durations without overlap
-        step(args.warmup + args.steps + i, P, 1, MAX_BATCH)
-    fence()
-    gpu.set_timing(False)
-    n_timed, stage_ms = gpu.timing_read()
+    n_timed, stage_ms = 0, [0.0] * 5
+    if args.kernel_samples > 0:
+        gpu.set_timing(True)
+        for i in range(args.kernel_samples):  # one lane, one launch per step: kernel durations without overlap
+            step(args.warmup + args.steps + i, P, 1, MAX_BATCH)
+        fence()
+        gpu.set_timing(False)
+        n_timed, stage_ms = gpu.timing_read()
     # overlapped mode: one picture per GPU per step, consecutive steps on the two
     # submission lanes (the next step's workgroups fill the CUs while the previous
     # step drains; kernels overlap, so this is a chip-level rate, not a per-kernel one)
@@ -530,7 +558,7 @@ def main():
         band = band_8k_leg(gpu, S, W, D, dist, world, rank, dev, exts, comm, args.band_steps, fence)
 
     recs = sbres = None
-    if world == 1:  # the workload's own job (set 0, picture 0), as the timed steps run it, for the parity check
+    if world == 1 and args.full:  # the workload's own job (set 0, picture 0) as the timed steps run it, for parity
         chk = torch.zeros(chunk_bytes, dtype=torch.uint8, device=dev)
         gpu.submit_batch_device([sets[0][0]], [chk.data_ptr()], [chk.data_ptr() + rec_bytes] if with_sb else None,
                                 lane=0)
@@ -615,7 +643,8 @@ def main():
             "algorithmic_hbm_gbps": round(bps * value / 1e9, 1),
             "roofline": {"bound": bound, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                          "frac": round(achieved / HBM_PEAK_GBPS, 4), "traffic": traffic,
-                         "kernel": "ME pass: " + " -> ".join(n for k, n in enumerate(names) if stage_ms[k] > 0) +
+                         "kernel": "ME pass: " + (" -> ".join(n for k, n in enumerate(names) if stage_ms[k] > 0)
+                                                  or "its kernels are timed singly with --full") +
                                    " (one launch each, back to back on the library stream)",
                          "achieved_from": ("bytes_per_launch of the dominant kernel / its average launch "
                                            "duration (HIP events on its dispatches, one lane)"
@@ -641,6 +670,44 @@ def main():
     gpu.close()
     if world > 1:
         dist.destroy_process_group()
+
+
+DUMP_BYTES = 60_000_000  # float data of one dump (the .npy headers included, under 64 MB in all)
+
+
+def dump_outputs(path, S, raw, n_pic, chunk_bytes, rec_bytes, begin, count, R, with_sb, prefix=""):
+    """--dump-outputs: `raw`, the bytes of one step's output buffer (per picture
+    its records [count][R], then its per-SB results [count]), as
+    path/<prefix>records_<field>.npy [rows][R]... and path/<prefix>sb_<field>.npy
+    [rows]..., a row being one (picture, SB) of the step. Every value is exact:
+    8- and 16-bit fields as float32, 32- and 64-bit ones as float64 (hme_sad, the
+    one 64-bit field, is a SAD, far below 2^53); struct
+    padding is left out and best_sad of a reference that was not searched, which
+    the library leaves undefined, reads 0xFFFFFFFF (as svtme.records_checksum).
+    When all rows would exceed DUMP_BYTES, a fixed sample of them (seed 0, in
+    ascending order) is written; <prefix>rows.npy lists the rows' (picture of the
+    step, SB index)."""
+    recs = np.stack([np.frombuffer(raw, S.REF_RECORD_DTYPE, count * R, p * chunk_bytes).reshape(count, R)
+                     for p in range(n_pic)]).reshape(n_pic * count, R).copy()
+    recs["best_sad"][~recs["searched"].astype(bool)] = 0xFFFFFFFF
+    parts = [("records_", recs)]
+    if with_sb:
+        parts.append(("sb_", np.stack([np.frombuffer(raw, S.SB_RESULT_DTYPE, count, p * chunk_bytes + rec_bytes)
+                                       for p in range(n_pic)]).reshape(n_pic * count)))
+
+    def as_float(a):
+        return a.astype(np.float64 if a.dtype.itemsize >= 4 else np.float32)
+    fields = [(tag + f, arr[f]) for tag, arr in parts for f in arr.dtype.names if not f.startswith("pad")]
+    rows = n_pic * count
+    row_bytes = 16 + sum(as_float(a[:1]).nbytes for _, a in fields)
+    keep = np.arange(rows)
+    if rows * row_bytes > DUMP_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(rows, DUMP_BYTES // row_bytes, replace=False))
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, prefix + "rows.npy"),
+            np.stack([keep // count, begin + keep % count], axis=1).astype(np.float64))
+    for name, a in fields:
+        np.save(os.path.join(path, prefix + name + ".npy"), as_float(a[keep]))
 
 
 def rccl_version(torch):

@@ -4,7 +4,7 @@
 cd "$GRAFT_REPO_ROOT"
 export TMPDIR=/tmp
 O=${O:-gpurun_out/ab}; mkdir -p $O
-A="--no-upload --band-steps 0 --no-cpu-baseline --workload ${WL:-4k_p8} ${BENCH_ARGS:-}"
+A="--full --no-upload --band-steps 0 --no-cpu-baseline --workload ${WL:-4k_p8} ${BENCH_ARGS:-}"
 for r in $(seq 1 ${ROUNDS:-2}); do
   timeout -k 10 200 python3 -u bench.py $A > $O/cur_$r.json 2>> $O/err || exit 1
   for L in ${LIBS:-}; do

@@ -7,6 +7,6 @@ for L in $LIBS; do
   echo "$L $(tail -1 $O/t_$L.log)"
 done
 for r in $(seq 1 ${ROUNDS:-3}); do for WL in $WLS; do for L in $LIBS; do
-  SVTME_LIB=svt-av1-mirror_amd/$L.so timeout -k 10 200 python3 bench.py --workload $WL --steps ${STEPS:-50} --warmup 10 --no-cpu-baseline --band-steps 0 > $O/b_${L}_${WL}_r$r.json 2> $O/b_${L}_${WL}_r$r.err || { tail $O/b_${L}_${WL}_r$r.err; exit 1; }
+  SVTME_LIB=svt-av1-mirror_amd/$L.so timeout -k 10 200 python3 bench.py --workload $WL --steps ${STEPS:-50} --warmup 10 --full --no-cpu-baseline --band-steps 0 > $O/b_${L}_${WL}_r$r.json 2> $O/b_${L}_${WL}_r$r.err || { tail $O/b_${L}_${WL}_r$r.err; exit 1; }
   python3 -c "import json,sys; d=json.load(open(sys.argv[1])); r=d['roofline']; print(sys.argv[1].split('/')[-1], round(d['value']/1e6,2), {k: v['avg_ms'] for k, v in r['stages'].items()})" $O/b_${L}_${WL}_r$r.json
 done; done; done

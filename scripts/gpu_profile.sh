@@ -8,7 +8,7 @@ mkdir -p $O
 export TMPDIR=/tmp
 { echo "nproc $(nproc)"; python3 -c "import os; print('affinity', len(os.sched_getaffinity(0)), 'cpu_count', os.cpu_count())";
   cat /sys/fs/cgroup/cpu.max 2>/dev/null; grep -m1 "model name" /proc/cpuinfo; } > $O/host.txt 2>&1
-timeout -k 10 300 python3 -u bench.py --workload $WL --steps 50 --warmup 10 ${BENCH_ARGS:-} > $O/bench.json 2> $O/bench.err || { echo "bench failed"; tail -20 $O/bench.err; exit 1; }
+timeout -k 10 300 python3 -u bench.py --workload $WL --steps 50 --warmup 10 --full ${BENCH_ARGS:-} > $O/bench.json 2> $O/bench.err || { echo "bench failed"; tail -20 $O/bench.err; exit 1; }
 cat $O/bench.json
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$GRAFT_REPO_ROOT/$O/kt" -o run --output-format csv -- python3 bench.py --workload $WL --steps 50 --warmup 10 --no-cpu-baseline --no-single-picture --no-upload --no-records-only --band-steps 0 --lanes 1 > $O/kt.log 2>&1 || { echo "rocprof kt failed"; tail -20 $O/kt.log; exit 1; }
 run_pass() {

@@ -9,7 +9,7 @@ O=gpurun_out/rehearsal; mkdir -p $O
 for EX in owner allgather; do
   timeout -k 10 300 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node ${NPROC:-2} --master-addr 127.0.0.1 \
     --master-port 29517 bench.py --gpus ${NPROC:-2} --steps 5 --warmup 2 --backend gloo --shared-device --exchange $EX \
-    --no-cpu-baseline --no-upload --band-steps 5 > $O/rehearsal_$EX.json 2> $O/rehearsal_$EX.err \
+    --full --no-cpu-baseline --no-upload --band-steps 5 > $O/rehearsal_$EX.json 2> $O/rehearsal_$EX.err \
     || { echo "rehearsal $EX failed"; tail -30 $O/rehearsal_$EX.err; exit 1; }
   tail -1 $O/rehearsal_$EX.json | python3 -c "import json,sys; d=json.load(sys.stdin); b=d['band_8k']; print('$EX', d['ranks'], d['config']['parallelism'], b['distribute_ms'], b['step_ms'])"
 done

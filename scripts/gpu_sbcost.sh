@@ -4,7 +4,7 @@ cd "$GRAFT_REPO_ROOT"
 export TMPDIR=/tmp
 O=${O:-gpurun_out/sbcost}; mkdir -p $O
 timeout -k 10 60 rocprofv3 -L > $O/rocprof_L.txt 2>&1 || true
-A="--no-upload --band-steps 0 --no-cpu-baseline"
+A="--full --no-upload --band-steps 0 --no-cpu-baseline"
 for r in 1 2; do
   timeout -k 10 200 python3 -u bench.py $A > $O/sb_$r.json 2>> $O/err || exit 1
   timeout -k 10 200 python3 -u bench.py $A --records-only > $O/ro_$r.json 2>> $O/err || exit 1
