@@ -456,6 +456,56 @@ void *svtme_device_records(svtme_ctx *ctx, uint64_t *bytes);
 /* The HIP stream (hipStream_t) the context launches on, for event timing. */
 void *svtme_stream(svtme_ctx *ctx);
 
+/* ---------------------------------------------------------------------------
+ * Dynamic-GOP detector: the early HME search of picture decision
+ * (TASK_DG_DETECTOR_HME, me_process.c:327-333; dg_detector_hme_level0 and
+ * early_hme, pd_process.c:393-634) as one job per picture pair. Per 64x64 SB
+ * the 16x16 block of the current picture's sixteenth plane is searched
+ * exhaustively (full SAD) over the search area on the reference picture's
+ * sixteenth plane; the per-SB results give the frame metrics the detector
+ * compares. Both pictures are resident (svtme_picture_upload*).
+ * ------------------------------------------------------------------------- */
+#define SVTME_DG_MAX_PAIRS 8
+#define SVTME_DG_MAX_SA 128
+
+typedef struct svtme_dg_pair {
+    uint64_t cur_picture_number; /* the "src" picture of early_hme (pd_process.c:592-598) */
+    uint64_t ref_picture_number;
+} svtme_dg_pair;
+
+typedef struct svtme_dg_sb { /* 8 bytes, one per SB in raster b64 order */
+    uint32_t sad;            /* hme_level0_sad */
+    int16_t mv_x, mv_y;      /* sr_center.col / .row, already x4 (pd_process.c:484-487) */
+} svtme_dg_sb;
+
+typedef struct svtme_dg_metrics { /* 32 bytes */
+    uint64_t tot_dist;            /* DGDetectorMetrics, pcs.h:732-735 */
+    uint32_t tot_cplx, tot_active;
+    int32_t sum_in_vectors;
+    int16_t mv_in_out_count;      /* PictureDecisionContext fields, pd_process.h:122-125, */
+    uint8_t perc_cplx, perc_active;
+    uint64_t norm_dist;           /* derived exactly as pd_process.c:630-633 */
+} svtme_dg_metrics;
+
+/* The reference's search area for an EbInputResolution: <= 360p 16x16,
+ * <= 480p 64x64, else 128x128 (pd_process.c:497-498). */
+void svtme_dg_search_area(int input_resolution, uint16_t *sa_width, uint16_t *sa_height);
+
+/* Host only, no GPU: the frame metrics of a width x height picture from its
+ * svtme_sb_total(width, height) per-SB results (pd_process.c:543-580, 630-633). */
+void svtme_dg_reduce(uint32_t width, uint32_t height, const svtme_dg_sb *sb, svtme_dg_metrics *out);
+
+/* The search of n pairs (1 .. SVTME_DG_MAX_PAIRS, all of one picture size: the
+ * three pairs of one decision, pd_process.c:672-718) in one launch on lane 0's
+ * stream. metrics receives n entries; sb_out is NULL or receives
+ * n x svtme_sb_total(width, height) per-SB results (host memory). sa_width is
+ * rounded up to a multiple of 8 as the reference does and, so rounded, is at
+ * most SVTME_DG_MAX_SA, as is sa_height. The call waits for a pending
+ * asynchronous upload of either picture on the GPU and is synchronous: it
+ * returns when the outputs are written. */
+svtme_status svtme_dg_detect(svtme_ctx *ctx, const svtme_dg_pair *pairs, uint32_t n, uint16_t sa_width,
+                             uint16_t sa_height, svtme_dg_metrics *metrics, svtme_dg_sb *sb_out);
+
 /* Number of 64x64 SBs of a width x height picture, and R for a job. */
 uint32_t svtme_sb_total(uint32_t width, uint32_t height);
 uint32_t svtme_job_ref_slots(const svtme_job *job);

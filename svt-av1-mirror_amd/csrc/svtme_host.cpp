@@ -42,6 +42,10 @@ extern "C" hipError_t svtme_launch_host_rows(const uint8_t *src, uint32_t src_st
                                              uint32_t dst_stride, hipStream_t s);
 extern "C" hipError_t svtme_prime_pack(void);
 extern "C" hipError_t svtme_prime_stages(void);
+extern "C" hipError_t svtme_prime_dg(void);
+extern "C" hipError_t svtme_launch_dg(const DevPlane *cur, const DevPlane *ref, uint32_t n, uint32_t width,
+                                      uint32_t height, uint16_t sa_w, uint16_t sa_h, svtme_dg_metrics *d_acc,
+                                      svtme_dg_sb *d_sb, hipStream_t s);
 extern "C" void svtme_stage_a_list(const svtme_job *job, uint8_t *list, uint32_t *count);
 extern "C" void svtme_stage_b_list(const svtme_job *job, uint8_t *list, uint32_t *count);
 extern "C" void svtme_stage_a1_list(const svtme_job *job, uint8_t *list, uint32_t *count);
@@ -160,6 +164,8 @@ struct svtme_ctx {
     size_t records_cap          = 0;
     svtme_sb_result *d_sb       = nullptr;
     size_t sb_cap               = 0;
+    void *d_dg    = nullptr; // svtme_dg_detect: n metrics slots | n x SBs per-SB results
+    size_t dg_cap = 0;
     uint32_t last_count = 0, last_R = 0;
     bool last_has_sb    = false;
     // job tables: a ring of device slots of SVTME_MAX_BATCH DevJobs, copied from
@@ -222,7 +228,7 @@ extern "C" svtme_status svtme_ctx_create(int device, svtme_ctx **out) {
     c->lanes[0].s = c->stream;
     // the code objects of the kernels, loaded now rather than at a first job's launches
     if ((e = svtme_prime_pyramid()) != hipSuccess || (e = svtme_prime_pack()) != hipSuccess ||
-        (e = svtme_prime_stages()) != hipSuccess) {
+        (e = svtme_prime_stages()) != hipSuccess || (e = svtme_prime_dg()) != hipSuccess) {
         (void)hipStreamDestroy(c->stream);
         delete c;
         return fail(SVTME_ERR_UNDEFINED, "svtme_ctx_create: loading the kernels: %s", hipGetErrorString(e));
@@ -292,6 +298,8 @@ extern "C" void svtme_ctx_destroy(svtme_ctx *c) {
         (void)hipFree(c->d_records);
     if (c->d_sb)
         (void)hipFree(c->d_sb);
+    if (c->d_dg)
+        (void)hipFree(c->d_dg);
     for (auto &set : c->tev)
         for (auto &e : set)
             if (e)
@@ -1525,6 +1533,111 @@ extern "C" svtme_status svtme_submit_picture(svtme_ctx *c, const svtme_job *job,
     if (st)
         return st;
     return fetch_locked(c, recs, sb);
+}
+
+// ----------------------------------------------------------------------------
+// dynamic-GOP detector (dg_detector_hme_level0 / early_hme, pd_process.c:492-634)
+// ----------------------------------------------------------------------------
+extern "C" void svtme_dg_search_area(int input_resolution, uint16_t *sa_width, uint16_t *sa_height) {
+    // INPUT_SIZE_360p_RANGE = 1, INPUT_SIZE_480p_RANGE = 2 (definitions.h:2079-2085)
+    const uint16_t sa = input_resolution <= 1 ? 16 : input_resolution <= 2 ? 64 : 128;
+    if (sa_width)
+        *sa_width = sa;
+    if (sa_height)
+        *sa_height = sa;
+}
+
+// the four derived fields from the accumulated ones (early_hme, pd_process.c:627-633): C integer
+// division (toward zero for a negative sum_in_vectors) and the narrowing of the context's fields
+static void dg_finish(uint32_t width, uint32_t height, svtme_dg_metrics *m) {
+    const uint32_t sbs   = svtme_sb_total(width, height);
+    m->mv_in_out_count = (int16_t)(m->sum_in_vectors * 100 / (int)sbs);
+    m->norm_dist       = m->tot_dist / sbs;
+    m->perc_cplx       = (uint8_t)((m->tot_cplx * 100) / sbs);
+    m->perc_active     = (uint8_t)((m->tot_active * 100) / sbs);
+}
+
+extern "C" void svtme_dg_reduce(uint32_t width, uint32_t height, const svtme_dg_sb *sb, svtme_dg_metrics *out) {
+    if (!sb || !out || !width || !height)
+        return;
+    const uint32_t wb = (width + 63) / 64, hb = (height + 63) / 64;
+    svtme_dg_metrics m{};
+    for (uint32_t y = 0; y < hb; y++)
+        for (uint32_t x = 0; x < wb; x++) {
+            const svtme_dg_sb &s = sb[y * wb + x];
+            m.tot_dist += s.sad;
+            m.tot_cplx += s.sad > 16 * 16 * 30;
+            m.tot_active += s.mv_x != 0 || s.mv_y != 0;
+            // does the vector point inwards or outwards? (the middle row / column counts nothing)
+            const int sy = s.mv_y > 0 ? 1 : s.mv_y < 0 ? -1 : 0, sx = s.mv_x > 0 ? 1 : s.mv_x < 0 ? -1 : 0;
+            m.sum_in_vectors += y < hb / 2 ? -sy : y > hb / 2 ? sy : 0;
+            m.sum_in_vectors += x < wb / 2 ? -sx : x > wb / 2 ? sx : 0;
+        }
+    dg_finish(width, height, &m);
+    *out = m;
+}
+
+// Held under the context lock from the launch to the copy-out, as svtme_submit_picture is:
+// the device outputs are the context's, and a release / invalidate of either picture from
+// another thread waits for the lock (the pictures are marked as read by lane 0 besides).
+extern "C" svtme_status svtme_dg_detect(svtme_ctx *c, const svtme_dg_pair *pairs, uint32_t n, uint16_t sa_width,
+                                        uint16_t sa_height, svtme_dg_metrics *metrics, svtme_dg_sb *sb_out) {
+    if (!c || !pairs || !metrics)
+        return fail(SVTME_ERR_BAD_PARAMETER, "svtme_dg_detect: null ctx, pairs or metrics");
+    if (n < 1 || n > SVTME_DG_MAX_PAIRS)
+        return fail(SVTME_ERR_BAD_PARAMETER, "svtme_dg_detect: %u pairs (1..%d)", n, SVTME_DG_MAX_PAIRS);
+    if (!sa_width || !sa_height || ((sa_width + 7u) & ~7u) > SVTME_DG_MAX_SA || sa_height > SVTME_DG_MAX_SA)
+        return fail(SVTME_ERR_BAD_PARAMETER, "svtme_dg_detect: search area %ux%u (1..%d, the width rounded up to 8)",
+                    sa_width, sa_height, SVTME_DG_MAX_SA);
+    std::lock_guard<std::mutex> lk(c->mu);
+    PicBuf *pb[SVTME_DG_MAX_PAIRS][2];
+    for (uint32_t k = 0; k < n; k++) {
+        const uint64_t pn[2] = {pairs[k].cur_picture_number, pairs[k].ref_picture_number};
+        for (int i = 0; i < 2; i++) {
+            auto it = c->pics.find(pn[i]);
+            if (it == c->pics.end())
+                return fail(SVTME_ERR_BAD_PARAMETER, "svtme_dg_detect: picture %llu is not resident",
+                            (unsigned long long)pn[i]);
+            pb[k][i] = &it->second;
+        }
+        if (pb[k][0]->W != pb[k][1]->W || pb[k][0]->H != pb[k][1]->H)
+            return fail(SVTME_ERR_BAD_PARAMETER, "svtme_dg_detect: pair %u: picture %llu is %ux%u, picture %llu %ux%u", k,
+                        (unsigned long long)pn[0], pb[k][0]->W, pb[k][0]->H, (unsigned long long)pn[1], pb[k][1]->W,
+                        pb[k][1]->H);
+        if (pb[k][0]->W != pb[0][0]->W || pb[k][0]->H != pb[0][0]->H)
+            return fail(SVTME_ERR_BAD_PARAMETER, "svtme_dg_detect: pair %u is %ux%u, pair 0 %ux%u: one size per call", k,
+                        pb[k][0]->W, pb[k][0]->H, pb[0][0]->W, pb[0][0]->H);
+    }
+    const uint32_t W = pb[0][0]->W, H = pb[0][0]->H, sbs = svtme_sb_total(W, H);
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t acc_bytes = sizeof(svtme_dg_metrics) * SVTME_DG_MAX_PAIRS;
+    svtme_status st        = ensure_buf(&c->d_dg, &c->dg_cap, acc_bytes + sizeof(svtme_dg_sb) * (size_t)n * sbs);
+    if (st)
+        return st;
+    DevPlane cur[SVTME_DG_MAX_PAIRS], ref[SVTME_DG_MAX_PAIRS];
+    for (uint32_t k = 0; k < n; k++) {
+        for (int i = 0; i < 2; i++)
+            if ((st = join_upload(c, *pb[k][i], 0)))
+                return st;
+        cur[k] = pb[k][0]->pyr.lv[2];
+        ref[k] = pb[k][1]->pyr.lv[2];
+    }
+    Lane &L               = c->lanes[0];
+    svtme_dg_metrics *d_m = (svtme_dg_metrics *)c->d_dg;
+    svtme_dg_sb *d_sb     = (svtme_dg_sb *)((uint8_t *)c->d_dg + acc_bytes);
+    HIP_TRY(hipMemsetAsync(d_m, 0, sizeof(svtme_dg_metrics) * n, L.s));
+    HIP_TRY(svtme_launch_dg(cur, ref, n, W, H, sa_width, sa_height, d_m, d_sb, L.s));
+    hipEvent_t done = L.ev[L.ev_next];
+    L.ev_next       = (L.ev_next + 1) % Lane::kEv;
+    HIP_TRY(hipEventRecord(done, L.s));
+    for (uint32_t k = 0; k < n; k++)
+        pb[k][0]->used[0] = pb[k][1]->used[0] = done;
+    HIP_TRY(hipMemcpyAsync(metrics, d_m, sizeof(svtme_dg_metrics) * n, hipMemcpyDeviceToHost, L.s));
+    if (sb_out)
+        HIP_TRY(hipMemcpyAsync(sb_out, d_sb, sizeof(svtme_dg_sb) * (size_t)n * sbs, hipMemcpyDeviceToHost, L.s));
+    HIP_TRY(hipStreamSynchronize(L.s));
+    for (uint32_t k = 0; k < n; k++) dg_finish(W, H, &metrics[k]);
+    return SVTME_OK;
 }
 
 extern "C" void *svtme_device_records(svtme_ctx *c, uint64_t *bytes) {

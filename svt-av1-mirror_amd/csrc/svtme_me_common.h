@@ -113,6 +113,14 @@ __device__ __forceinline__ int wave_incl_scan(int v) {
 __device__ __forceinline__ uint32_t magic_u32(uint32_t d) { return 0xFFFFFFFFu / d + 1u; }
 __device__ __forceinline__ int mdiv(int n, uint32_t m) { return m ? (int)__umulhi((uint32_t)n, m) : n; }
 
+// XCD-aware block order: blocks b and b + 8 share an XCD (round-robin
+// dispatch), so each XCD gets one contiguous band of work whose reference
+// windows overlap in its L2 (bijective for any grid size)
+__device__ __forceinline__ uint32_t xcd_remap(uint32_t bid, uint32_t nwg) {
+    const uint32_t xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
+    return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+}
+
 #define UNI(x) __builtin_amdgcn_readfirstlane((int)(x))
 __device__ __forceinline__ uint32_t rl32(uint32_t v, int l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, l); }
 __device__ __forceinline__ uint64_t rl64(uint64_t v, int l) {

@@ -379,14 +379,6 @@ __device__ __forceinline__ SbGeo sb_geo(const DevJob &dj, uint32_t sb_local) {
     return g;
 }
 
-// XCD-aware block order: blocks b and b + 8 share an XCD (round-robin
-// dispatch), so each XCD gets one contiguous band of work whose reference
-// windows overlap in its L2 (bijective for any grid size)
-__device__ __forceinline__ uint32_t xcd_remap(uint32_t bid, uint32_t nwg) {
-    const uint32_t xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
-    return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-}
-
 // the job of work unit u of a batch launch, and u's index inside that job. The
 // job table is read through the constant address space: it is written before
 // the launch and never during it, so the compiler may keep its fields in SGPRs

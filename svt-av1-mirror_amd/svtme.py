@@ -208,6 +208,27 @@ class PackLayout(C.Structure):
                 ("full_records", C.c_uint8), ("sb_results", C.c_uint8), ("pad", C.c_uint8 * 2)]
 
 
+# Dynamic-GOP detector (include/svtme.h svtme_dg_*)
+DG_MAX_PAIRS, DG_MAX_SA = 8, 128
+DG_SB_DTYPE = np.dtype([("sad", "<u4"), ("mv_x", "<i2"), ("mv_y", "<i2")])
+assert DG_SB_DTYPE.itemsize == 8
+
+
+class DgPair(C.Structure):
+    _fields_ = [("cur_picture_number", C.c_uint64), ("ref_picture_number", C.c_uint64)]
+
+
+class DgMetrics(C.Structure):
+    """svtme_dg_metrics: the accumulated DGDetectorMetrics (pcs.h:732-735) and the
+    four values early_hme derives from them (pd_process.c:630-633)."""
+    _fields_ = [("tot_dist", C.c_uint64), ("tot_cplx", C.c_uint32), ("tot_active", C.c_uint32),
+                ("sum_in_vectors", C.c_int32), ("mv_in_out_count", C.c_int16), ("perc_cplx", C.c_uint8),
+                ("perc_active", C.c_uint8), ("norm_dist", C.c_uint64)]
+
+    def as_dict(self) -> dict:
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
 TAIL_BYTES = 24  # svtme_record_tail: the last 24 bytes of svtme_ref_record
 
 
@@ -645,8 +666,32 @@ def _job_api_protos(lib):
         _proto(lib, "svtme_derive_controls_tf", "restype", None)
         _proto(lib, "svtme_sb_total", "argtypes", [C.c_uint32, C.c_uint32])
         _proto(lib, "svtme_sb_total", "restype", C.c_uint32)
+        _proto(lib, "svtme_dg_search_area", "argtypes", [C.c_int, C.POINTER(C.c_uint16), C.POINTER(C.c_uint16)])
+        _proto(lib, "svtme_dg_search_area", "restype", None)
+        _proto(lib, "svtme_dg_reduce", "argtypes", [C.c_uint32, C.c_uint32, vp, C.POINTER(DgMetrics)])
+        _proto(lib, "svtme_dg_reduce", "restype", None)
+        _proto(lib, "svtme_dg_detect", "argtypes", [vp, C.POINTER(DgPair), C.c_uint32, C.c_uint16, C.c_uint16,
+                                                    C.POINTER(DgMetrics), vp])
+        _proto(lib, "svtme_dg_detect", "restype", C.c_int32)
         lib._svtme_protos = True
     return lib
+
+
+def dg_search_area(input_resolution: int):
+    """svtme_dg_search_area: the detector's (sa_width, sa_height) for an EbInputResolution."""
+    w, h = C.c_uint16(), C.c_uint16()
+    load_product().svtme_dg_search_area(input_resolution, C.byref(w), C.byref(h))
+    return w.value, h.value
+
+
+def dg_reduce(width: int, height: int, sb: np.ndarray) -> DgMetrics:
+    """svtme_dg_reduce (host only): the frame metrics from the per-SB results of one pair."""
+    sb = np.ascontiguousarray(sb, DG_SB_DTYPE)
+    if sb.size != sb_total(width, height):
+        raise ValueError(f"{sb.size} per-SB results for a {width}x{height} picture ({sb_total(width, height)} SBs)")
+    m = DgMetrics()
+    load_product().svtme_dg_reduce(width, height, sb.ctypes.data, C.byref(m))
+    return m
 
 
 class GpuME:
@@ -852,6 +897,24 @@ class GpuME:
         self._check(self.lib.svtme_fetch(self.ctx, recs.ctypes.data, sbr.ctypes.data if sbr is not None else None),
                     "svtme_fetch")
         return recs, sbr
+
+    def dg_detect(self, pairs, sa_w: int, sa_h: int, with_sb: bool = True):
+        """svtme_dg_detect: the dynamic-GOP detector's search of (cur, ref) picture-number
+        pairs in one launch -> ([DgMetrics] per pair, per-SB results [n, sbs] or None)."""
+        n = len(pairs)
+        arr = (DgPair * max(n, 1))(*[DgPair(int(c), int(r)) for c, r in pairs])
+        met = (DgMetrics * max(n, 1))()
+        sb = None
+        if with_sb:
+            # sized from the first pair's resident picture (an unknown picture: the call reports it)
+            w, h = C.c_uint32(), C.c_uint32()
+            st = self.lib.svtme_picture_download(self.ctx, int(pairs[0][0]), 2, None, None, C.byref(w), C.byref(h),
+                                                 None) if n else 0
+            sbs = sb_total(w.value * 4, h.value * 4) if st == 0 and n else 0
+            sb = np.zeros((n, max(sbs, 1)), DG_SB_DTYPE)
+        self._check(self.lib.svtme_dg_detect(self.ctx, arr, n, sa_w, sa_h, met, sb.ctypes.data if with_sb else None),
+                    "svtme_dg_detect")
+        return list(met)[:n], sb
 
     def device_records(self):
         n = C.c_uint64()
