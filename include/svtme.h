@@ -506,6 +506,76 @@ void svtme_dg_reduce(uint32_t width, uint32_t height, const svtme_dg_sb *sb, svt
 svtme_status svtme_dg_detect(svtme_ctx *ctx, const svtme_dg_pair *pairs, uint32_t n, uint16_t sa_width,
                              uint16_t sa_height, svtme_dg_metrics *metrics, svtme_dg_sb *sb_out);
 
+/* ---------------------------------------------------------------------------
+ * Temporal filtering: the sub-pel refinement that follows the TF-ME call
+ * (temporal_filtering.c:3177-3336, up to but not including the first
+ * tf_64x64_inter_prediction / tf_32x32_inter_prediction) as one job per picture
+ * window. Per (reference picture, 64x64 SB) the 64x64, 32x32, 16x16 and
+ * optionally 8x8 blocks are refined from the full-pel winners of the TF-ME job
+ * (SVTME_ME_MCTF, full records) by half, quarter and eighth-pel steps: AV1
+ * interpolation of the reference block, variance against the centre picture.
+ * 8-bit path only (8-bit input, or 10-bit input with tf_ctrls.use_8bit_subpel,
+ * on the MSB plane the library holds).
+ * ------------------------------------------------------------------------- */
+/* The tf_ctrls / MeContext fields the stage reads (definitions.h:167-209,
+ * me_context.h:496-497). The caller passes them; nothing is derived from a preset. */
+typedef struct svtme_tf_subpel_controls {
+    uint8_t half_pel_mode;          /* 0 off, 1 all 8 neighbours, 2 / 3 no diagonals (0..3) */
+    uint8_t quarter_pel_mode;       /* the same (0..3) */
+    uint8_t eight_pel_mode;         /* 0 off, 1 all 8 neighbours (0..1) */
+    uint8_t use_2tap;               /* 64x64 and 32x32 blocks: 1 bilinear, 0 8-tap regular (0..1) */
+    uint8_t sub_sampling_shift;     /* variance over every (1 << shift)-th row (0..1) */
+    uint8_t enable_8x8_pred;        /* search the 8x8 blocks (0..1) */
+    uint8_t use_pred_64x64_only_th; /* tf_use_64x64_pred threshold, 0 = off */
+    uint8_t subpel_early_exit_th;   /* running-best early exit per pixel, 0 = off */
+    uint64_t pred_error_32x32_th;   /* 32x32 error under which its 16x16 search is bypassed */
+} svtme_tf_subpel_controls; /* 16 bytes */
+
+/* svtme_tf_subpel_sb.branch */
+#define SVTME_TFSP_64_ONLY 0   /* 64x64 only: use_pred_64x64_only_th (tf_use_64x64_pred) or the TF-ME early exit */
+#define SVTME_TFSP_64_CHOSEN 1 /* 64x64 chosen after the 32x32 search (temporal_filtering.c:3265) */
+#define SVTME_TFSP_32 2        /* the 32x32 path: 16x16 (8x8) searches and the split flags */
+
+#define SVTME_TFSP_BLOCKS 85   /* 1 + 4 + 16 + 64 */
+#define SVTME_TFSP_OFF_32 1    /* block index: idx_32x32 */
+#define SVTME_TFSP_OFF_16 5    /* idx_32x32 * 4 + idx_16x16 */
+#define SVTME_TFSP_OFF_8 21    /* idx_32x32 * 16 + 4 * idx_16x16 + idx_8x8 */
+#define SVTME_TFSP_UNSET_ERROR 0x7FFFFFFFu /* INT_MAX: the reference's initial block error */
+
+/* Per (reference, SB) result, the reference's own index orders (me_context.h:472-486).
+ * Blocks the reference leaves unwritten on the branch taken hold MV 0 and error
+ * INT_MAX. On the two 64x64 branches the 32x32 MVs are the 64x64 MV and the flags 0
+ * (convert_64x64_info_to_32x32_info), the 32x32 errors INT_MAX (they belong to the
+ * final prediction). Where 8x8 replaces 16x16 the 16x16 error is the 8x8 sum
+ * (derive_tf_32x32_block_split_flag). */
+typedef struct svtme_tf_subpel_sb {
+    struct {
+        int16_t x, y; /* 1/8 pel */
+    } mv[SVTME_TFSP_BLOCKS];
+    uint32_t error[SVTME_TFSP_BLOCKS];
+    uint8_t split_32x32[4];    /* tf_32x32_block_split_flag */
+    uint8_t split_16x16[4][4]; /* tf_16x16_block_split_flag */
+    uint8_t branch;            /* SVTME_TFSP_* */
+    uint8_t pad[3];
+} svtme_tf_subpel_sb; /* 704 bytes */
+#ifdef __cplusplus
+static_assert(sizeof(svtme_tf_subpel_sb) == 704 && sizeof(svtme_tf_subpel_controls) == 16, "svtme_tf_subpel layout");
+#else
+_Static_assert(sizeof(svtme_tf_subpel_sb) == 704 && sizeof(svtme_tf_subpel_controls) == 16, "svtme_tf_subpel layout");
+#endif
+
+/* The refinement of n references (1 .. SVTME_MAX_BATCH_JOBS) of one window against
+ * the centre picture, in one launch on lane 0's stream. All pictures are resident
+ * and width x height (the aligned size of the TF-ME jobs). `records` holds
+ * n x svtme_sb_total(width, height) records in host memory: slot 0 of each TF-ME
+ * job in the order of ref_picture_numbers; `out` receives as many results.
+ * Synchronous; returns SVTME_ERR_BAD_PARAMETER before any GPU work for a NULL
+ * ctx / ref_picture_numbers / controls / records / out, n out of range, a control
+ * above its range, a picture that is not resident or has another size. */
+svtme_status svtme_tf_subpel(svtme_ctx *ctx, uint64_t centre_picture_number, const uint64_t *ref_picture_numbers,
+                             uint32_t n, uint32_t width, uint32_t height, const svtme_tf_subpel_controls *controls,
+                             const svtme_ref_record *records, svtme_tf_subpel_sb *out);
+
 /* Number of 64x64 SBs of a width x height picture, and R for a job. */
 uint32_t svtme_sb_total(uint32_t width, uint32_t height);
 uint32_t svtme_job_ref_slots(const svtme_job *job);

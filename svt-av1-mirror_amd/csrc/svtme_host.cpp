@@ -46,6 +46,10 @@ extern "C" hipError_t svtme_prime_dg(void);
 extern "C" hipError_t svtme_launch_dg(const DevPlane *cur, const DevPlane *ref, uint32_t n, uint32_t width,
                                       uint32_t height, uint16_t sa_w, uint16_t sa_h, svtme_dg_metrics *d_acc,
                                       svtme_dg_sb *d_sb, hipStream_t s);
+extern "C" hipError_t svtme_prime_tfsp(void);
+extern "C" hipError_t svtme_launch_tfsp(const DevPlane *cen, const DevPlane *ref, uint32_t n, uint32_t width,
+                                        uint32_t height, const svtme_tf_subpel_controls *ctl,
+                                        const svtme_ref_record *d_rec, svtme_tf_subpel_sb *d_out, hipStream_t s);
 extern "C" void svtme_stage_a_list(const svtme_job *job, uint8_t *list, uint32_t *count);
 extern "C" void svtme_stage_b_list(const svtme_job *job, uint8_t *list, uint32_t *count);
 extern "C" void svtme_stage_a1_list(const svtme_job *job, uint8_t *list, uint32_t *count);
@@ -166,6 +170,8 @@ struct svtme_ctx {
     size_t sb_cap               = 0;
     void *d_dg    = nullptr; // svtme_dg_detect: n metrics slots | n x SBs per-SB results
     size_t dg_cap = 0;
+    void *d_tfsp    = nullptr; // svtme_tf_subpel: n x SBs records | n x SBs results
+    size_t tfsp_cap = 0;
     uint32_t last_count = 0, last_R = 0;
     bool last_has_sb    = false;
     // job tables: a ring of device slots of SVTME_MAX_BATCH DevJobs, copied from
@@ -228,7 +234,8 @@ extern "C" svtme_status svtme_ctx_create(int device, svtme_ctx **out) {
     c->lanes[0].s = c->stream;
     // the code objects of the kernels, loaded now rather than at a first job's launches
     if ((e = svtme_prime_pyramid()) != hipSuccess || (e = svtme_prime_pack()) != hipSuccess ||
-        (e = svtme_prime_stages()) != hipSuccess || (e = svtme_prime_dg()) != hipSuccess) {
+        (e = svtme_prime_stages()) != hipSuccess || (e = svtme_prime_dg()) != hipSuccess ||
+        (e = svtme_prime_tfsp()) != hipSuccess) {
         (void)hipStreamDestroy(c->stream);
         delete c;
         return fail(SVTME_ERR_UNDEFINED, "svtme_ctx_create: loading the kernels: %s", hipGetErrorString(e));
@@ -300,6 +307,8 @@ extern "C" void svtme_ctx_destroy(svtme_ctx *c) {
         (void)hipFree(c->d_sb);
     if (c->d_dg)
         (void)hipFree(c->d_dg);
+    if (c->d_tfsp)
+        (void)hipFree(c->d_tfsp);
     for (auto &set : c->tev)
         for (auto &e : set)
             if (e)
@@ -1637,6 +1646,68 @@ extern "C" svtme_status svtme_dg_detect(svtme_ctx *c, const svtme_dg_pair *pairs
         HIP_TRY(hipMemcpyAsync(sb_out, d_sb, sizeof(svtme_dg_sb) * (size_t)n * sbs, hipMemcpyDeviceToHost, L.s));
     HIP_TRY(hipStreamSynchronize(L.s));
     for (uint32_t k = 0; k < n; k++) dg_finish(W, H, &metrics[k]);
+    return SVTME_OK;
+}
+
+// ----------------------------------------------------------------------------
+// Temporal filtering's sub-pel refinement (svtme_tfsp.hip). Held under the context
+// lock from the launch to the copy-out, as svtme_dg_detect is.
+// ----------------------------------------------------------------------------
+extern "C" svtme_status svtme_tf_subpel(svtme_ctx *c, uint64_t centre_picture_number,
+                                        const uint64_t *ref_picture_numbers, uint32_t n, uint32_t width,
+                                        uint32_t height, const svtme_tf_subpel_controls *ctl,
+                                        const svtme_ref_record *records, svtme_tf_subpel_sb *out) {
+    if (!c || !ref_picture_numbers || !ctl || !records || !out)
+        return fail(SVTME_ERR_BAD_PARAMETER, "svtme_tf_subpel: null ctx, ref_picture_numbers, controls, records or out");
+    if (n < 1 || n > SVTME_MAX_BATCH_JOBS)
+        return fail(SVTME_ERR_BAD_PARAMETER, "svtme_tf_subpel: %u references (1..%d)", n, SVTME_MAX_BATCH_JOBS);
+    if (ctl->half_pel_mode > 3 || ctl->quarter_pel_mode > 3 || ctl->eight_pel_mode > 1 || ctl->use_2tap > 1 ||
+        ctl->sub_sampling_shift > 1 || ctl->enable_8x8_pred > 1)
+        return fail(SVTME_ERR_BAD_PARAMETER,
+                    "svtme_tf_subpel: controls out of range: half %u quarter %u (0..3), eighth %u, use_2tap %u, "
+                    "sub_sampling_shift %u, enable_8x8_pred %u (0..1)",
+                    ctl->half_pel_mode, ctl->quarter_pel_mode, ctl->eight_pel_mode, ctl->use_2tap,
+                    ctl->sub_sampling_shift, ctl->enable_8x8_pred);
+    if (!width || !height)
+        return fail(SVTME_ERR_BAD_PARAMETER, "svtme_tf_subpel: %ux%u picture", width, height);
+    const uint32_t W = svtme_align8_u(width), H = svtme_align8_u(height);
+    std::lock_guard<std::mutex> lk(c->mu);
+    PicBuf *pb[SVTME_MAX_BATCH_JOBS + 1];
+    for (uint32_t k = 0; k <= n; k++) {
+        const uint64_t pn = k ? ref_picture_numbers[k - 1] : centre_picture_number;
+        auto it           = c->pics.find(pn);
+        if (it == c->pics.end())
+            return fail(SVTME_ERR_BAD_PARAMETER, "svtme_tf_subpel: picture %llu is not resident", (unsigned long long)pn);
+        pb[k] = &it->second;
+        if (pb[k]->W != W || pb[k]->H != H)
+            return fail(SVTME_ERR_BAD_PARAMETER, "svtme_tf_subpel: picture %llu is %ux%u, the window %ux%u",
+                        (unsigned long long)pn, pb[k]->W, pb[k]->H, W, H);
+    }
+    const uint32_t sbs = svtme_sb_total(W, H);
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t rec_bytes = sizeof(svtme_ref_record) * (size_t)n * sbs;
+    const size_t out_bytes = sizeof(svtme_tf_subpel_sb) * (size_t)n * sbs;
+    svtme_status st        = ensure_buf(&c->d_tfsp, &c->tfsp_cap, rec_bytes + out_bytes);
+    if (st)
+        return st;
+    DevPlane ref[SVTME_MAX_BATCH_JOBS];
+    for (uint32_t k = 0; k <= n; k++) {
+        if ((st = join_upload(c, *pb[k], 0)))
+            return st;
+        if (k)
+            ref[k - 1] = pb[k]->pyr.lv[0];
+    }
+    Lane &L                   = c->lanes[0];
+    svtme_ref_record *d_rec   = (svtme_ref_record *)c->d_tfsp;
+    svtme_tf_subpel_sb *d_out = (svtme_tf_subpel_sb *)((uint8_t *)c->d_tfsp + rec_bytes);
+    HIP_TRY(hipMemcpyAsync(d_rec, records, rec_bytes, hipMemcpyHostToDevice, L.s));
+    HIP_TRY(svtme_launch_tfsp(&pb[0]->pyr.lv[0], ref, n, W, H, ctl, d_rec, d_out, L.s));
+    hipEvent_t done = L.ev[L.ev_next];
+    L.ev_next       = (L.ev_next + 1) % Lane::kEv;
+    HIP_TRY(hipEventRecord(done, L.s));
+    for (uint32_t k = 0; k <= n; k++) pb[k]->used[0] = done;
+    HIP_TRY(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, L.s));
+    HIP_TRY(hipStreamSynchronize(L.s));
     return SVTME_OK;
 }
 

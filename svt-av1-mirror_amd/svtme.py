@@ -229,6 +229,39 @@ class DgMetrics(C.Structure):
         return {name: int(getattr(self, name)) for name, _ in self._fields_}
 
 
+# Temporal filtering's sub-pel refinement (include/svtme.h svtme_tf_subpel*)
+MAX_BATCH_JOBS = 16  # SVTME_MAX_BATCH_JOBS
+TFSP_64_ONLY, TFSP_64_CHOSEN, TFSP_32 = 0, 1, 2
+TFSP_BLOCKS, TFSP_OFF_32, TFSP_OFF_16, TFSP_OFF_8 = 85, 1, 5, 21
+TFSP_UNSET_ERROR = 0x7FFFFFFF
+TF_SUBPEL_SB_DTYPE = np.dtype(
+    [
+        ("mv", [("x", "<i2"), ("y", "<i2")], (TFSP_BLOCKS,)),
+        ("error", "<u4", (TFSP_BLOCKS,)),
+        ("split_32x32", "u1", (4,)),
+        ("split_16x16", "u1", (4, 4)),
+        ("branch", "u1"),
+        ("pad", "u1", (3,)),
+    ]
+)
+assert TF_SUBPEL_SB_DTYPE.itemsize == 704
+
+
+class TfSubpelControls(C.Structure):
+    """svtme_tf_subpel_controls: the tf_ctrls / MeContext fields the refinement reads."""
+    _fields_ = [("half_pel_mode", C.c_uint8), ("quarter_pel_mode", C.c_uint8), ("eight_pel_mode", C.c_uint8),
+                ("use_2tap", C.c_uint8), ("sub_sampling_shift", C.c_uint8), ("enable_8x8_pred", C.c_uint8),
+                ("use_pred_64x64_only_th", C.c_uint8), ("subpel_early_exit_th", C.c_uint8),
+                ("pred_error_32x32_th", C.c_uint64)]
+
+    @staticmethod
+    def from_dict(d: dict) -> "TfSubpelControls":
+        return TfSubpelControls(**{k: int(v) for k, v in d.items()})
+
+    def as_dict(self) -> dict:
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
 TAIL_BYTES = 24  # svtme_record_tail: the last 24 bytes of svtme_ref_record
 
 
@@ -673,6 +706,9 @@ def _job_api_protos(lib):
         _proto(lib, "svtme_dg_detect", "argtypes", [vp, C.POINTER(DgPair), C.c_uint32, C.c_uint16, C.c_uint16,
                                                     C.POINTER(DgMetrics), vp])
         _proto(lib, "svtme_dg_detect", "restype", C.c_int32)
+        _proto(lib, "svtme_tf_subpel", "argtypes", [vp, C.c_uint64, C.POINTER(C.c_uint64), C.c_uint32, C.c_uint32,
+                                                    C.c_uint32, C.POINTER(TfSubpelControls), vp, vp])
+        _proto(lib, "svtme_tf_subpel", "restype", C.c_int32)
         lib._svtme_protos = True
     return lib
 
@@ -915,6 +951,22 @@ class GpuME:
         self._check(self.lib.svtme_dg_detect(self.ctx, arr, n, sa_w, sa_h, met, sb.ctypes.data if with_sb else None),
                     "svtme_dg_detect")
         return list(met)[:n], sb
+
+    def tf_subpel(self, centre: int, refs, width: int, height: int, controls: TfSubpelControls,
+                  records: np.ndarray) -> np.ndarray:
+        """svtme_tf_subpel: temporal filtering's sub-pel refinement of the references `refs`
+        (picture numbers) against the centre picture; records[len(refs), SBs] are slot 0 of the
+        TF-ME jobs (full records) -> results [len(refs), SBs] of TF_SUBPEL_SB_DTYPE."""
+        n = len(refs)
+        sbs = sb_total(align8(width), align8(height))
+        records = np.ascontiguousarray(records, REF_RECORD_DTYPE)
+        if records.size != n * sbs:
+            raise ValueError(f"{records.size} records for {n} references x {sbs} SBs")
+        arr = (C.c_uint64 * max(n, 1))(*[int(r) for r in refs])
+        out = np.zeros((n, sbs), TF_SUBPEL_SB_DTYPE)
+        self._check(self.lib.svtme_tf_subpel(self.ctx, int(centre), arr, n, width, height, C.byref(controls),
+                                             records.ctypes.data, out.ctypes.data), "svtme_tf_subpel")
+        return out
 
     def device_records(self):
         n = C.c_uint64()
