@@ -2,10 +2,14 @@
 
 Expected values are the fixtures tests/golden/tfsp_cases.{json,npz}: the
 reference's own planes, ME records, svt_inter_predictor and variance kernels
-under the control flow restated in tests/golden/make_golden_tfsp.py. CPU tests
-pin the ABI, the parameter checks that need no context and the fixtures
-themselves; GPU tests compare svtme_tf_subpel bit-exactly, as whole structs,
-against the fixtures.
+under the control flow restated in tests/golden/make_golden_tfsp.py. Beside them
+stands a model of the whole refinement in numpy (tests/tfsp_model.py: the same
+control flow around the AV1 specification's filters), which needs nothing from
+the reference. CPU tests pin the ABI, the parameter checks that need no context,
+the fixtures themselves, the model to the fixtures and, where the reference is
+built, the model to the reference on the random sweep's inputs; GPU tests
+compare svtme_tf_subpel bit-exactly, as whole structs, against the fixtures and,
+on the sweep's inputs, against the model.
 """
 import ctypes as C
 import json
@@ -26,6 +30,8 @@ for p in (GOLD, HERE):
         sys.path.insert(0, p)
 
 import make_golden_tfsp as G  # noqa: E402
+import tfsp_model as M  # noqa: E402
+from tfsp_model import SPEC_REGULAR, numpy_distortion  # noqa: E402,F401
 
 DOC = json.load(open(os.path.join(GOLD, "tfsp_cases.json")))
 TFSP_CASES = DOC["cases"]
@@ -59,22 +65,37 @@ def test_tfsp_case_list_matches_generator():
 
 
 def test_tfsp_control_sets_cover_the_modes():
+    assert {c["controls"] for c in TFSP_CASES} == set(G.CONTROL_SETS)  # every set is used
     sets = [G.CONTROL_SETS[c["controls"]] for c in TFSP_CASES]
-    assert {s["half_pel_mode"] for s in sets} >= {1, 2}
-    for field in ("use_2tap", "sub_sampling_shift", "enable_8x8_pred"):
+    # every value the host accepts (svtme_tf_subpel's range checks)
+    assert {s["half_pel_mode"] for s in sets} == {0, 1, 2, 3}
+    assert {s["quarter_pel_mode"] for s in sets} == {0, 1, 2, 3}
+    for field in ("eight_pel_mode", "use_2tap", "sub_sampling_shift", "enable_8x8_pred"):
         assert {s[field] for s in sets} == {0, 1}, field
-    for field in ("subpel_early_exit_th", "pred_error_32x32_th", "use_pred_64x64_only_th"):
-        assert any(s[field] for s in sets), field
+    assert {s["use_pred_64x64_only_th"] for s in sets} == {0, 10, 35, 200}
+    assert {s["subpel_early_exit_th"] for s in sets} == {0, 1, 2, 4, 8}
+    assert {s["pred_error_32x32_th"] for s in sets} == {0, 8 * 32 * 32, 20 * 32 * 32, G.U64_MAX}
+    # combinations: no half-pel stage before a quarter-pel stage; bilinear at 64/32 beside the regular
+    # filter at 16/8; 8x8 blocks on 4 kept rows
+    assert any(s["half_pel_mode"] == 0 and s["quarter_pel_mode"] for s in sets)
+    assert any(s["use_2tap"] and s["enable_8x8_pred"] for s in sets)
+    assert any(s["sub_sampling_shift"] and s["enable_8x8_pred"] for s in sets)
     assert "l8" in {c["controls"] for c in TFSP_CASES}  # the level preset 8 uses
-    assert {(c["w"], c["h"]) for c in TFSP_CASES} == {(128, 128), (192, 136)}
-    assert {len(c["refs"]) for c in TFSP_CASES} >= {1, 3}
-    assert {c["records"] for c in TFSP_CASES} == {"me", "edges"}
+    assert {(c["w"], c["h"]) for c in TFSP_CASES} == {(128, 128), (192, 136), (72, 40), (200, 72), (124, 66)}
+    assert {len(c["refs"]) for c in TFSP_CASES} == {1, 3, 5}
+    assert all(len(set(c["refs"] + [c["centre"]])) == len(c["refs"]) + 1 for c in TFSP_CASES)  # distinct pictures
+    assert {c["records"] for c in TFSP_CASES} == {"me", "edges", "wrap"}
+    assert all((c["seed"] is not None) == (c["records"] == "wrap") for c in TFSP_CASES)
+    assert {c["kind"] for c in TFSP_CASES} == {"frac", "glide", "same", "flat", "noise"}
 
 
 def test_tfsp_coverage_counts_are_all_non_zero():
     assert set(DOC["coverage"]) == set(G.COVERAGE_KEYS)
     zero = [k for k, v in DOC["coverage"].items() if not v > 0]
     assert zero == []
+    assert set(DOC["coverage_per_case"]) == {c["id"] for c in TFSP_CASES}
+    for k in G.COVERAGE_KEYS:
+        assert sum(c.get(k, 0) for c in DOC["coverage_per_case"].values()) == DOC["coverage"][k], k
 
 
 def test_tfsp_fixture_shapes(svtme, gold):
@@ -188,40 +209,6 @@ def test_tfsp_bad_parameters_without_a_device(svtme):
     assert fake.raw == bytes(64)
 
 
-# AV1 specification, Subpel_Filters[0] (EIGHTTAP_REGULAR), phases 0..8; phase 16 - p is phase p
-# mirrored, and every phase sums to 128. The bilinear filter is 128 - 8 p, 8 p.
-_SPEC_HALF = [[0, 0, 0, 128, 0, 0, 0, 0], [0, 2, -6, 126, 8, -2, 0, 0], [0, 2, -10, 122, 18, -4, 0, 0],
-              [0, 2, -12, 116, 28, -8, 2, 0], [0, 2, -14, 110, 38, -10, 2, 0], [0, 2, -14, 102, 48, -12, 2, 0],
-              [0, 2, -16, 94, 58, -12, 2, 0], [0, 2, -14, 84, 66, -12, 2, 0], [0, 2, -14, 76, 76, -14, 2, 0]]
-SPEC_REGULAR = np.array(_SPEC_HALF + [_SPEC_HALF[16 - p][::-1] for p in range(9, 16)], np.int64)
-assert (SPEC_REGULAR.sum(axis=1) == 128).all()
-
-
-def numpy_distortion(cen, ref, pad, W, H, b, px, py, mvx, mvy, bil, ss):
-    """The distortion of one position by the AV1 specification's filters and the rounding of the
-    single-reference convolve (round_0 3, round_1 11), independent of the reference's code."""
-    qx, _, _ = G.clamp(mvx, px, b, W)
-    qy, _, _ = G.clamp(mvy, py, b, H)
-    fx, fy, x0, y0 = qx & 15, qy & 15, px + (qx >> 4), py + (qy >> 4)
-    taps = (lambda p: np.array([0, 0, 0, 128 - 8 * p, 8 * p, 0, 0, 0], np.int64)) if bil else (lambda p: SPEC_REGULAR[p])
-    win = ref[pad + y0 - 3:pad + y0 + b + 4, pad + x0 - 3:pad + x0 + b + 4].astype(np.int64)
-    if fx and fy:
-        im = ((1 << 14) + sum(taps(fx)[k] * win[:, k:k + b] for k in range(8)) + 4) >> 3
-        s = (1 << 19) + sum(taps(fy)[k] * im[k:k + b] for k in range(8))
-        pred = ((s + 1024) >> 11) - 384
-    elif fx:
-        pred = (((sum(taps(fx)[k] * win[3:3 + b, k:k + b] for k in range(8)) + 4) >> 3) + 8) >> 4
-    elif fy:
-        pred = (sum(taps(fy)[k] * win[k:k + b, 3:3 + b] for k in range(8)) + 64) >> 7
-    else:
-        pred = win[3:3 + b, 3:3 + b]
-    pred = np.clip(pred, 0, 255)[::1 << ss]
-    d = pred - cen[pad + py:pad + py + b:1 << ss, pad + px:pad + px + b].astype(np.int64)
-    total, sse = int(d.sum()), int((d * d).sum())
-    q = abs(total * total) // (b * (b >> ss))
-    return ((sse - q) & 0xFFFFFFFF) << ss
-
-
 @pytest.mark.parametrize("name", ["frac128_l2", "frac128_l8_w3", "edges192_l8"])
 def test_tfsp_fixture_errors_vs_specification_filters(svtme, gold, name):
     """Every block error of a fixture at its winning MV, recomputed with the filter taps of the AV1
@@ -257,6 +244,68 @@ def test_tfsp_fixture_regenerates(gold):
     rec, out = G.generate_case(case)
     assert rec.tobytes() == gold[case["id"] + ".rec"].tobytes()
     assert out.tobytes() == gold[case["id"] + ".out"].tobytes()
+
+
+def case_controls(case):
+    return {f: G.CONTROL_SETS[case["controls"]][f] for f in G.SUBPEL_FIELDS}
+
+
+@pytest.mark.parametrize("case", TFSP_CASES, ids=lambda c: c["id"])
+def test_tfsp_model_equals_fixture(svtme, gold, case):
+    """The numpy model (tests/tfsp_model.py) on the oracle's planes gives every fixture as whole
+    structs, and counts what the reference-side run of the generator counted."""
+    pyr = {t: svtme.build_host_pyramid(f, "oracle") for t, f in G.case_frames(case).items()}
+    out, cover = M.refine_window(pyr[case["centre"]], [pyr[r] for r in case["refs"]], case_controls(case),
+                                 gold[case["id"] + ".rec"])
+    assert_structs_equal(out, gold[case["id"] + ".out"], case["id"])
+    assert {k: v for k, v in cover.items() if v} == DOC["coverage_per_case"][case["id"]]
+
+
+# The random sweep (tests/tfsp_model.py: sweep_case): (seed, references or None for the seed's own draw).
+# Seeds 9 and 12 draw full windows of 16 distinct references; 32 and 54 are there for the SBs that
+# choose the 64x64 block after the 32x32 search, which the perturbed records seldom leave.
+SWEEP = [(seed, None) for seed in list(range(24)) + [32, 54]]
+_sweep_cache = {}
+
+
+def sweep_expected(seed, n):
+    """-> (case, the oracle's ME records, the sweep's records, the model's results, its coverage),
+    computed once per process."""
+    if (seed, n) not in _sweep_cache:
+        case = M.sweep_case(seed, n)
+        _sweep_cache[(seed, n)] = (case,) + M.sweep_model(case)
+    return _sweep_cache[(seed, n)]
+
+
+def test_tfsp_sweep_covers_every_branch(svtme):
+    """The sweep's cases, by the model alone: together they reach every coverage count, old and
+    new, every shape, content and value of the controls, and a full window."""
+    cases = [sweep_expected(seed, n)[0] for seed, n in SWEEP]
+    total = {k: sum(sweep_expected(seed, n)[4][k] for seed, n in SWEEP) for k in G.COVERAGE_KEYS}
+    print("sweep coverage:", total)
+    assert [k for k, v in total.items() if not v > 0] == []
+    assert {(c["w"], c["h"]) for c in cases} == set(M.SWEEP_SHAPES)
+    assert {c["kind"] for c in cases} == set(M.SWEEP_KINDS)
+    assert {len(c["refs"]) for c in cases} >= {1, svtme.MAX_BATCH_JOBS}
+    assert all(len(set(c["refs"] + [c["centre"]])) == len(c["refs"]) + 1 for c in cases)
+    for field, values in (("half_pel_mode", range(4)), ("quarter_pel_mode", range(4)), ("eight_pel_mode", range(2)),
+                          ("use_2tap", range(2)), ("sub_sampling_shift", range(2)), ("enable_8x8_pred", range(2)),
+                          ("subpel_early_exit_th", M.SWEEP_EXIT_TH), ("use_pred_64x64_only_th", M.SWEEP_64_ONLY_TH),
+                          ("pred_error_32x32_th", M.SWEEP_ERR_32_TH)):
+        assert {c["subpel"][field] for c in cases} == set(values), field
+
+
+@pytest.mark.skipif(not ref_available(), reason="oracle/_ref not built (needs the reference's sources)")
+@pytest.mark.parametrize("seed,n", SWEEP, ids=[f"seed{s}" for s, _ in SWEEP])
+def test_tfsp_model_equals_reference_on_sweep(svtme, seed, n):
+    """The reference-backed evaluation (the reference's planes, svt_inter_predictor and variance
+    kernels) on the sweep's inputs, which are no fixtures: the same structs and counts as the model."""
+    case, _, recs, want, want_cover = sweep_expected(seed, n)
+    pyr = {t: svtme.build_host_pyramid(f, "ref") for t, f in M.sweep_frames(case).items()}
+    cover = {k: 0 for k in G.COVERAGE_KEYS}
+    out = G.refine_window(pyr[case["centre"]], [pyr[r] for r in case["refs"]], case["subpel"], recs, cover)
+    assert_structs_equal(want, out, f"seed {seed} controls {case['subpel']}")
+    assert cover == want_cover
 
 
 # ----------------------------------------------------------------------------
@@ -299,6 +348,31 @@ def test_tfsp_vs_reference_golden(svtme, gpu, gold, case):
     try:
         out = run_case(gpu, case, gold[case["id"] + ".rec"])
         assert_structs_equal(out, gold[case["id"] + ".out"], case["id"])
+    finally:
+        release_case(gpu, frames)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("seed,n", SWEEP, ids=[f"seed{s}" for s, _ in SWEEP])
+def test_tfsp_random_sweep_vs_model(svtme, gpu, seed, n):
+    """Random shapes, contents, windows and controls: the records of the GPU's own TF-ME jobs (the
+    oracle's, checked here), perturbed, then svtme_tf_subpel against the numpy model as whole structs."""
+    case, want_me, recs, want, _ = sweep_expected(seed, n)
+    what = f"seed {seed}: {case['w']}x{case['h']} {case['kind']}, references {case['refs']}, controls {case['subpel']}"
+    frames = M.sweep_frames(case)
+    for t, f in frames.items():
+        gpu.upload(BASE + t, f)
+    try:
+        layout = svtme.PackLayout(n_pus=85, max_cand=1, max_refs=1, full_records=1, sb_results=0)
+        me = []
+        for r in case["refs"]:
+            packed = gpu.submit_packed(G.me_job(case, case["controls"], r, BASE), layout)
+            me.append(np.frombuffer(packed, svtme.REF_RECORD_DTYPE))
+        me = np.stack(me)
+        assert svtme.compare_records(want_me.reshape(-1, 1), me.reshape(-1, 1)) == [], what
+        out = gpu.tf_subpel(BASE + case["centre"], [BASE + r for r in case["refs"]], case["w"], case["h"],
+                            svtme.TfSubpelControls.from_dict(case["subpel"]), M.sweep_records(case, me))
+        assert_structs_equal(out, want, what)
     finally:
         release_case(gpu, frames)
 
