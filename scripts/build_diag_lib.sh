@@ -15,7 +15,7 @@ T=$(mktemp -d)
 trap 'rm -rf "$T"' EXIT
 FL="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall"
 /opt/rocm/bin/hipcc $FL -include $C/diag/svtme_diag.h "$@" -c -o $T/stages.o $C/svtme_stages.hip
-for f in svtme_pyramid.hip svtme_pack.hip svtme_rtcd.hip svtme_host.cpp; do
+for f in svtme_pyramid.hip svtme_pack.hip svtme_rtcd.hip svtme_dg.hip svtme_tfsp.hip svtme_host.cpp; do
   /opt/rocm/bin/hipcc $FL -c -o $T/$f.o $C/$f
 done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o svt-av1-mirror_amd/libsvtme_$NAME.so $T/*.o

@@ -60,8 +60,10 @@ def main():
     np.save(os.path.join(ROOT, "gpurun_out", f"stamps_{name}_x{P}.npy"), st)
     rt, ids, st_w = st[:, 8:10], st[:, 10:12], st[:, 12:16]
     wv = st[:, 24:32]  # per wavefront: phase-0 work done, full-pel records done
+    nw = 4 if wv[:, 3].any() else 3  # wavefronts per workgroup (svtme_hme_waves): wave 3 stamps nothing at 3
     if wv.any():
-        for w in range(4):
+        print(f"  {nw} wavefronts per workgroup")
+        for w in range(nw):
             print(f"  wave {w}: phase-0 work done at mean {np.mean(wv[:, w] - st[:, 0]):7.0f} cycles after start; "
                   f"full-pel records done {np.mean(wv[:, 4 + w] - st[:, 16]):7.0f} after the final centre")
     fp = st[:, 22:24]  # wave 0's record: search area (check_00_center, probe) done, search done
@@ -101,8 +103,8 @@ def main():
     key = xcc * 1000 + se * 100 + cu
     _, cnt = np.unique(key, return_counts=True)
     simd = (st_w >> 4) & 3
-    print("  SIMD of waves 0-3, share of WGs with wave w on SIMD (w + r) & 3, r = 0..3:",
-          [[round(float(np.mean(simd[:, w] == ((w + r) & 3))), 2) for r in range(4)] for w in range(4)])
+    print(f"  SIMD of waves 0-{nw - 1}, share of WGs with wave w on SIMD (w + r) & 3, r = 0..3:",
+          [[round(float(np.mean(simd[:, w] == ((w + r) & 3))), 2) for r in range(4)] for w in range(nw)])
     print(f"  distinct CUs {len(cnt)}; WGs per CU min {cnt.min()} p50 {np.median(cnt):.0f} max {cnt.max()}")
     gpu.close()
 

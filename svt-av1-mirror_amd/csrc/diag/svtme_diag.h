@@ -18,7 +18,8 @@
 __device__ unsigned long long g_hme_stamps[1 << 17][32];
 // slots 0-7 shader clock per phase; 8 / 9 the 100 MHz real-time clock at the
 // first / latest stamp; 10 XCC_ID, 11 HW_ID (CU, SE) register values; 12-15
-// HW_ID of waves 0-3; 16 shader clock after the final search centre (HME_STOP(55))
+// HW_ID of waves 0-3 (a workgroup of three wavefronts, svtme_hme_waves, leaves wave 3's
+// slots at 0); 16 shader clock after the final search centre (HME_STOP(55))
 #define HME_STAMP(k)                                                                                                   \
     do {                                                                                                               \
         if (threadIdx.x == 0 && blockIdx.x < (1u << 17)) {                                                             \

@@ -1062,7 +1062,7 @@ __device__ __forceinline__ SlotCentre final_centre(const svtme_job &job, const B
 }
 
 // ----------------------------------------------------------------------------
-// k_hme: stages A, D and B of one SB fused in one workgroup (4 wavefronts).
+// k_hme: stages A, D and B of one SB fused in one workgroup (4 or 3 wavefronts).
 // Used when every SB of the job is 64 wide, the HME searches sub-sample rows
 // (hme_search_method SUB_SAD) and level 2 is off (svtme_hme_fused); other jobs
 // run k_stage_a -> k_stage_d -> k_stage_b. Both write the same BState.
@@ -1617,7 +1617,8 @@ __device__ void fullpel(StC &st, const DevPlane &C, uint32_t ox, uint32_t oy) {
 // st.keys (dead once the keys are decoded into st.rec; stage_c_tail zeroes it).
 // finish_sb_out: waves 2-3 store the image up to me_distortion in 16-byte pieces
 // while wave 0 (compute_distortion) and wave 1 (GM detection) finish the last words
-// and store them themselves: no zero fill of the HBM copy, no scattered byte stores
+// and store them themselves (in a workgroup of three waves, wave 1 then stores wave
+// 3's half): no zero fill of the HBM copy, no scattered byte stores
 // to HBM.
 __device__ __forceinline__ void finish_sb_cands(StC &st, const DevJob &dj, uint32_t sb_local, uint32_t bw, uint32_t bh) {
     static_assert(sizeof(svtme_sb_result) % 4 == 0 && sizeof(svtme_sb_result) <= sizeof(st.keys) &&
@@ -1784,6 +1785,7 @@ __device__ __forceinline__ void finish_sb_cands(StC &st, const DevJob &dj, uint3
     }
 }
 
+template <int NW = 4>
 __device__ __forceinline__ void finish_sb_out(StC &st, const DevJob &dj, uint32_t sb_local, uint32_t bw, uint32_t bh) {
     static_assert(offsetof(svtme_sb_result, me_8x8_cost_variance) ==
                           offsetof(svtme_sb_result, me_distortion) + 4 * SVTME_PU_COUNT &&
@@ -1800,10 +1802,10 @@ __device__ __forceinline__ void finish_sb_out(StC &st, const DevJob &dj, uint32_
     uint32_t *img      = (uint32_t *)&st.keys[0][0];
     svtme_sb_result *o = (svtme_sb_result *)img;
     uint32_t *ow       = (uint32_t *)(dj.out_sb + sb_local);
-    if (wid >= 2) {
-        // the image up to me_distortion: the result is 4-byte aligned (sizeof 4796),
-        // so up to 3 head words, 16-byte stores, up to 3 tail words
-        const int t     = tid - 128;
+    // the image up to me_distortion by 128 threads, t the thread's index among them: the
+    // result is 4-byte aligned (sizeof 4796), so up to 3 head words, 16-byte stores,
+    // up to 3 tail words
+    auto store_image = [&](int t) {
         const int head  = (int)((16u - ((uint32_t)(uintptr_t)ow & 15u)) & 15u) >> 2;
         const int n16   = (NIMG - head) >> 2;
         const int tail0 = head + 4 * n16;
@@ -1818,6 +1820,9 @@ __device__ __forceinline__ void finish_sb_out(StC &st, const DevJob &dj, uint32_
             else if (j >= 4 && tail0 + (j - 4) < NIMG)
                 ow[tail0 + (j - 4)] = img[tail0 + (j - 4)];
         }
+    };
+    if (wid >= 2) {
+        store_image(tid - 128);
     } else if (wid == 0) {
         // compute_distortion (motion_estimation.c:2964-3007): lane-parallel sums; the 6 words to HBM
         uint32_t w6 = 0;
@@ -1906,13 +1911,17 @@ __device__ __forceinline__ void finish_sb_out(StC &st, const DevJob &dj, uint32_
         }
         if (lane < 2)
             ow[WGM + lane] = lane == 0 ? flags : 0u;
-    }}
+        if (NW == 3) // three waves: the second half of the image after the GM detection
+            store_image(64 + lane);
+    }
+}
 
+template <int NW = 4>
 __device__ __forceinline__ void finish_sb(StC &st, const DevJob &dj, uint32_t sb_local, uint32_t bw, uint32_t bh) {
     finish_sb_cands(st, dj, sb_local, bw, bh);
     __syncthreads();
     HME_SUB(20);
-    finish_sb_out(st, dj, sb_local, bw, bh);
+    finish_sb_out<NW>(st, dj, sb_local, bw, bh);
 }
 
 // the records (sb_count x R, slots in list-0-then-list-1 order) by threads [t0, t0 + nt): the
@@ -1949,13 +1958,14 @@ __device__ __forceinline__ void write_records(const StC &st, const DevJob &dj, u
 // distortions / GM detection of one SB from its searched best SADs and MVs
 // (motion_estimation.c:1522-1565, 2520-3007); all threads of the workgroup
 // SUMS: st.sum8 holds the 8x8 sums of the searched slots (stage_e_body made them),
-// and the keys (under the svtme_sb_result image) are dead: waves 1-3 zero the image
-// while wave 0 prunes, then waves 0-1 build the candidate arrays while waves 2-3
-// write the records (one barrier less, the records off the critical path)
-template <bool SUMS>
+// and the keys (under the svtme_sb_result image) are dead: the waves from 1 zero the
+// image while wave 0 prunes, then waves 0-1 build the candidate arrays while the waves
+// from 2 write the records (one barrier less, the records off the critical path)
+template <bool SUMS, int NW = 4> // NW: wavefronts of the workgroup (k_hme: 3 or 4)
 __device__ __forceinline__ void stage_c_tail(StC &st, const DevJob &dj, uint32_t sb_local, uint32_t bw, uint32_t bh, uint32_t vmask) {
     const svtme_job &job    = dj.job;
     const svtme_controls &c = job.ctrl;
+    constexpr int NT = 64 * NW;
     const int tid = threadIdx.x, lane = tid & 63;
     const bool w0 = (tid >> 6) == 0;
     const bool sbr = dj.out_sb != nullptr;
@@ -1994,7 +2004,7 @@ __device__ __forceinline__ void stage_c_tail(StC &st, const DevJob &dj, uint32_t
         }
     }
     if (SUMS && sbr && !w0) // the svtme_sb_result image (finish_sb) starts zeroed
-        for (int i = tid - 64; i < (int)(sizeof(svtme_sb_result) + 15) / 16; i += 192)
+        for (int i = tid - 64; i < (int)(sizeof(svtme_sb_result) + 15) / 16; i += NT - 64)
             ((uint4 *)img)[i] = make_uint4(0, 0, 0, 0);
     __syncthreads();
     HME_SUB(17);
@@ -2002,22 +2012,22 @@ __device__ __forceinline__ void stage_c_tail(StC &st, const DevJob &dj, uint32_t
         if (tid < 128)
             finish_sb_cands(st, dj, sb_local, bw, bh);
         else
-            write_records(st, dj, sb_local, tid - 128, 128);
+            write_records(st, dj, sb_local, tid - 128, NT - 128);
         HME_SUB(18);
         __syncthreads();
         HME_SUB(20);
-        finish_sb_out(st, dj, sb_local, bw, bh);
+        finish_sb_out<NW>(st, dj, sb_local, bw, bh);
         HME_SUB(21);
         return;
     }
-    write_records(st, dj, sb_local, tid, 256);
+    write_records(st, dj, sb_local, tid, NT);
     HME_SUB(18);
     if (sbr) {
-        for (int i = tid; i < (int)(sizeof(svtme_sb_result) + 15) / 16; i += 256)
+        for (int i = tid; i < (int)(sizeof(svtme_sb_result) + 15) / 16; i += NT)
             ((uint4 *)img)[i] = make_uint4(0, 0, 0, 0);
         __syncthreads();
         HME_SUB(19);
-        finish_sb(st, dj, sb_local, bw, bh);
+        finish_sb<NW>(st, dj, sb_local, bw, bh);
         HME_SUB(21);
     }
 }
@@ -2791,6 +2801,12 @@ __device__ __forceinline__ void direct_record(svtme_ref_record *rec, const CSlot
     }
 }
 
+// the slot state of a record that is not searched (pruned, or the TF-ME early exit)
+__device__ __forceinline__ CSlot fp_unsearched(uint64_t hme_sad, uint32_t zz, int16_t sc_x, int16_t sc_y, uint8_t dref,
+                                               uint8_t tf_exit) {
+    return CSlot{hme_sad, zz, sc_x, sc_y, 0, 0, 0, 0, 0, 0, dref, 0, tf_exit};
+}
+
 template <bool SUB, bool K32, int TQ = (SUB ? FP_TQ : 2), bool WIDE = false, int WHOLE = 7>
 __device__ __forceinline__ void fp_slot(const DevJob &dj, const SbGeo &G, int s, const uint32_t (&src)[SUB ? 4 : 8][2],
                                         int by, int bx, uint64_t hme_sad, uint32_t zz, uint32_t rdiv, int16_t sc_x,
@@ -2800,7 +2816,7 @@ __device__ __forceinline__ void fp_slot(const DevJob &dj, const SbGeo &G, int s,
     const int l = s >> 2, r = s & 3;
     const uint32_t ox = G.ox, oy = G.oy;
     if (!dref || tf_exit) {
-        const CSlot cv{hme_sad, zz, sc_x, sc_y, 0, 0, 0, 0, 0, 0, dref, 0, tf_exit};
+        const CSlot cv = fp_unsearched(hme_sad, zz, sc_x, sc_y, dref, tf_exit);
         if (part == 0 && lane == 0)
             *cs = cv;
         if (rec)
@@ -3799,9 +3815,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))
 // Per SB: decode the argmin keys kb[k][85] of the R records (slot state cin[k])
 // into best SAD / MV per PU (strict-< first minimum in search order), then
 // stage_c_tail; all threads of the workgroup. reset: leave kb at ~0 (banded
-// jobs merge into it with atomic min). Wavefront w decodes the records w, w + 4
+// jobs merge into it with atomic min). Wavefront w decodes the records w, w + NW
 // whole (its lanes the 64 8x8 PUs, then 21 the larger ones) and sums the 8x8
 // best SADs of each for me_prune_ref on the way (st.sum8): no serial sums later.
+template <int NW = 4> // wavefronts of the workgroup
 __device__ __forceinline__ void stage_e_body(StC &st, const DevJob &dj, uint32_t sb_local,
                                              const SbGeo &G, uint32_t vmask, const CSlot *cin,
                                              unsigned long long *kb, bool reset) {
@@ -3829,7 +3846,7 @@ __device__ __forceinline__ void stage_e_body(StC &st, const DevJob &dj, uint32_t
     }
     // the records' decode reads its record's state straight from cin (not the slot
     // state above): no barrier between the two
-    for (int kk = wid; kk < R; kk += 4) {
+    for (int kk = wid; kk < R; kk += NW) {
         const int s      = kk < nr0 ? kk : 4 + (kk - nr0);
         const CSlot &v   = cin[kk];
         const bool srch  = v.searched != 0;
@@ -3869,7 +3886,7 @@ __device__ __forceinline__ void stage_e_body(StC &st, const DevJob &dj, uint32_t
             decode(lane, sad, mv); // 64x64, 32x32, 16x16
     }
     __syncthreads();
-    stage_c_tail<true>(st, dj, sb_local, G.bw, G.bh, vmask);
+    stage_c_tail<true, NW>(st, dj, sb_local, G.bw, G.bh, vmask);
 }
 
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) k_stage_e(const DevBatch B) {
@@ -4056,8 +4073,14 @@ struct HmeSh {
 #define HME_PRIO_HI() __builtin_amdgcn_s_setprio(2)
 #define HME_PRIO_LO() __builtin_amdgcn_s_setprio(0)
 #define HME_WAVES_PER_EU 8 // 64 VGPRs: 8 workgroups per CU
-template <bool FP, bool SUB_ME, bool K32, bool RT = false> // RT: the real-time tune's HME-L0 reduction (a1_table)
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(HME_WAVES_PER_EU, HME_WAVES_PER_EU))) k_hme(const DevBatch B) {
+// RT: the real-time tune's HME-L0 reduction (a1_table). NW: wavefronts per workgroup, 4 or 3
+// (svtme_hme_waves): every phase fits three waves in the same number of passes, and ten
+// 3-wave workgroups reside per CU where eight 4-wave ones do
+template <bool FP, bool SUB_ME, bool K32, bool RT = false, int NW = 4>
+__global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(HME_WAVES_PER_EU, HME_WAVES_PER_EU))) k_hme(const DevBatch B) {
+    static_assert(NW == 3 || NW == 4, "k_hme: 3 or 4 wavefronts");
+    static_assert(sizeof(HmeSh) <= 16384, "HmeSh: ten workgroups per CU (160 KB of LDS)");
+    constexpr int NT = 64 * NW; // threads
     __shared__ HmeSh sh;
     const int tid = threadIdx.x, lane = tid & 63, wid = UNI(tid >> 6);
     uint32_t sb_local;
@@ -4066,9 +4089,11 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(HME_WA
     const DevJob &gj = batch_job(B, xcd_remap(blockIdx.x, gridDim.x), &sb_local);
     {
         // one 16-byte load per thread (a loop of dword loads waited for each round trip)
-        static_assert(sizeof(DevJob) % 16 == 0 && sizeof(DevJob) / 16 <= 256, "DevJob: one uint4 per thread");
+        static_assert(sizeof(DevJob) % 16 == 0 && sizeof(DevJob) / 16 <= 2 * NT, "DevJob: at most two uint4 per thread");
         if (tid < (int)(sizeof(DevJob) / 16))
             ((uint4 *)&sh.dj)[tid] = ((const uint4 *)&gj)[tid];
+        if (sizeof(DevJob) / 16 > NT && tid + NT < (int)(sizeof(DevJob) / 16)) // (issued with the first: one round trip)
+            ((uint4 *)&sh.dj)[tid + NT] = ((const uint4 *)&gj)[tid + NT];
     }
     __syncthreads();
     const DevJob &dj        = sh.dj;
@@ -4088,7 +4113,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(HME_WA
     //           row x half row, two batches of loads in flight, then the zz decisions in the same
     //           wave (which searches the reference performs): no barrier between the two
     //   wave 1: A1 search table of every search the slots may need (geometry only)
-    //   waves 2-3: the full- and quarter-resolution source blocks of HME-L2 / HME-L1
+    //   waves 2 .. NW - 1: the full- and quarter-resolution source blocks of HME-L2 / HME-L1
     if (wid == 0) {
         dec_init(d);
         uint32_t accv = 0; // lane s: slot s's zz sum
@@ -4199,12 +4224,22 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(HME_WA
                           c.hme_search_method != SVTME_FULL_SAD_SEARCH && !(dj.paths & SVTME_PATH_NO_A1_GATE);
         a1_table<RT ? 1 : 0>(sh.u.a, dj, vmask, sox, soy, kh, 0, 0, 0, gate);
     } else {
-        // full-resolution source block (64 x 64, even rows) for HME-L2: waves 2-3
+        // full-resolution source block (64 x 64, even rows) for HME-L2: waves 2-3, or
+        // wave 2 in two passes with both loads issued before either LDS write
         if (c.enable_hme_level2_flag) {
             const DevPlane &F = dj.cur.lv[0];
-            const int row = (tid - 128) >> 2, part = tid & 3;
-            const u32x4a4 v = ldg4((const uint32_t *)(F.base + (ptrdiff_t)(G.oy + 2 * row) * F.stride + G.ox + 16 * part));
-            ((uint4 *)sh.u.a.src1[row])[part] = make_uint4(v.x, v.y, v.z, v.w);
+            constexpr int NP = 128 / (NT - 128);
+            u32x4a4 v[NP];
+#pragma unroll
+            for (int p = 0; p < NP; p++) {
+                const int i = tid - 128 + p * (NT - 128), row = i >> 2, part = i & 3;
+                v[p] = ldg4((const uint32_t *)(F.base + (ptrdiff_t)(G.oy + 2 * row) * F.stride + G.ox + 16 * part));
+            }
+#pragma unroll
+            for (int p = 0; p < NP; p++) {
+                const int i = tid - 128 + p * (NT - 128), row = i >> 2, part = i & 3;
+                ((uint4 *)sh.u.a.src1[row])[part] = make_uint4(v[p].x, v[p].y, v[p].z, v[p].w);
+            }
         }
         // quarter-resolution source block (32 x 32, even rows) for HME-L1: threads 128-159
         if (c.enable_hme_level1_flag && tid < 160) {
@@ -4238,7 +4273,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(HME_WA
         const int nitems3 = sh.u.a.nitems3, base2 = sh.u.a.base2, end1 = sh.u.a.end1, base3 = sh.u.a.base3;
         // round 1: items [0, end1); round 2 (gated list-1 pre-HME): [base3, nitems), after a barrier
         auto tiles = [&](auto fullk, int lo, int hi, bool gated) {
-            for (int it = lo + tid; it < hi; it += 256) {
+            for (int it = lo + tid; it < hi; it += NT) {
                 if (it >= nitems3 && it < base2)
                     continue; // the padding before the 2-row group
                 const HSrch &e = sh.u.a.srch[find_search(sh.u.a.srch, nsrch, it)];
@@ -4525,7 +4560,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(HME_WA
         const int nlanes = 4 * sh.u.a.nitems1, nsrch = sh.u.a.nsrch1;
         const int pstride = dj.cur.lv[1].stride;
         auto tiles = [&](auto fullk) {
-            for (int it4 = tid; it4 < nlanes; it4 += 256) {
+            for (int it4 = tid; it4 < nlanes; it4 += NT) {
                 const int it    = it4 >> 2;
                 const HSrch1 &e = sh.u.a.s1[find_search(sh.u.a.s1, nsrch, it)];
                 const int local = it - e.item0;
@@ -4597,7 +4632,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(HME_WA
             const int nlanes = 8 * sh.u.a.nitems1, nsrch = sh.u.a.nsrch1;
             const int pstride = dj.cur.lv[0].stride;
             const int kh2     = (int)(G.bh >> 1);
-            for (int it8 = tid; it8 < nlanes; it8 += 256) {
+            for (int it8 = tid; it8 < nlanes; it8 += NT) {
                 const int it    = it8 >> 3;
                 const HSrch1 &e = sh.u.a.s1[find_search(sh.u.a.s1, nsrch, it)];
                 const int local = it - e.item0;
@@ -4654,8 +4689,25 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(HME_WA
     __syncthreads();
     HME_PRIO_LO();
     HME_STOP(55);
-    for (int k = wid; k < (int)dj.R; k += 4) {
+    // the j-th record that searches (do_ref and no tf_exit: fp_slot's test) goes to wave
+    // j % NW; one that does not is only its CSlot, written by the last wave without
+    // a source block (a pruned record does not cost a searching wave a load round trip)
+    const int nrec = (int)dj.R, nr0 = (int)SF(gj.job, num_refs[0]);
+    const uint8_t tfx = (uint8_t)UNI(sh.tf_exit);
+    for (int k = 0, j = 0; k < nrec; k++) { // (every wave walks the records: k, j wave-uniform)
         constexpr int ROWS = SUB_ME ? 4 : 8, RSTEP = SUB_ME ? 2 : 1;
+        const int s         = k < nr0 ? k : 4 + (k - nr0);
+        const SlotCentre &v = sh.cen[s];
+        const bool srch     = UNI(v.do_ref) && !tfx;
+        const int owner     = srch ? j : NW - 1;
+        j                   = srch ? (j + 1 == NW ? 0 : j + 1) : j;
+        if (wid != owner)
+            continue;
+        if (!srch) {
+            if (lane == 0)
+                sh.cin[k] = fp_unsearched(v.hme_sad, v.zz, v.sc_x, v.sc_y, v.do_ref, tfx);
+            continue;
+        }
         // an opaque lane index: the block's address terms are made per record, not hoisted
         // out of this loop (live across it, they spill at 64 VGPRs)
         int fl = lane;
@@ -4676,18 +4728,15 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(HME_WA
             src[rr][0] = v[0];
             src[rr][1] = v[1];
         }
-        const int nr0       = (int)SF(gj.job, num_refs[0]);
-        const int s         = k < nr0 ? k : 4 + (k - nr0);
-        const SlotCentre &v = sh.cen[s];
         fp_slot<SUB_ME, K32, 2, false, HME_WHOLE>(gj, G, s, src, by, bx, rl64(v.hme_sad, 0), (uint32_t)UNI(v.zz), (uint32_t)UNI(v.reduce_div),
-                                (int16_t)UNI(v.sc_x), (int16_t)UNI(v.sc_y), (uint8_t)UNI(v.do_ref),
-                                (uint8_t)UNI(sh.tf_exit), 0, 1u, &sh.u.st.keys[k][0], &sh.cin[k]);
+                                (int16_t)UNI(v.sc_x), (int16_t)UNI(v.sc_y), (uint8_t)UNI(v.do_ref), tfx, 0, 1u,
+                                &sh.u.st.keys[k][0], &sh.cin[k]);
     }
     HME_WAVE(1);
     __syncthreads();
     HME_STAMP(6);
     // ---- E: decode, me_prune_ref, records, candidates / distortions / GM detection
-    stage_e_body(sh.u.st, gj, sb_local, G, vmask, sh.cin, &sh.u.st.keys[0][0], false);
+    stage_e_body<NW>(sh.u.st, gj, sb_local, G, vmask, sh.cin, &sh.u.st.keys[0][0], false);
     HME_STAMP(7);
 }
 
@@ -4810,6 +4859,27 @@ extern "C" bool svtme_hme_fused(const svtme_job *job) {
 // the same with the context's path selection (svtme_set_paths) applied
 static bool hme_fused(const DevJob &dj) { return svtme_hme_fused(&dj.job) && !(dj.paths & SVTME_PATH_NO_FUSED_HME); }
 
+// Wavefronts per workgroup of the whole-pass k_hme (one SB each): 3 where ten 3-wave
+// workgroups per CU measured faster than eight 4-wave ones, else 4. A pure function
+// of the job; SVTME_PATH_HME_4WAVES forces 4. Left at 4, not measured at 3: full-SAD
+// full-pel rows, the real-time tune's HME-L0 reduction, more than 4 records.
+extern "C" uint32_t svtme_hme_waves(const svtme_job *job) {
+    const svtme_controls &c = job->ctrl;
+    uint32_t R = 0;
+    for (int l = 0; l < job->num_lists && l < 2; l++) R += job->num_refs[l];
+    return c.me_search_method != SVTME_FULL_SAD_SEARCH && !svtme_hme_rt(&c) && R <= 4 ? 3u : 4u;
+}
+// the same under path selection `paths`
+extern "C" uint32_t svtme_hme_waves_paths(const svtme_job *job, uint32_t paths) {
+    return (paths & SVTME_PATH_HME_4WAVES) ? 4u : svtme_hme_waves(job);
+}
+// and for the launch: 4 wherever the whole-pass k_hme does not run
+static uint32_t hme_waves(const DevJob &dj) {
+    const bool whole = svtme_hme_fused(&dj.job) && dj.parts == 1 &&
+                       !(dj.paths & (SVTME_PATH_NO_FUSED_HME | SVTME_PATH_SPLIT_PASS));
+    return whole ? svtme_hme_waves_paths(&dj.job, dj.paths) : 4u;
+}
+
 // the real-time tune's HME-L0 reduction is on (get_hme_l0_search_area,
 // motion_estimation.c:1811-1819): k_hme<..., RT = true> only
 extern "C" bool svtme_hme_rt(const svtme_controls *c) {
@@ -4908,7 +4978,7 @@ extern "C" uint32_t svtme_launch_key(const DevJob *dj) {
            (uint32_t)(dj->parts == 1) << 5 | (uint32_t)svtme_fp_wide(&dj->job.ctrl) << 6 |
            (uint32_t)svtme_hme_rt(&dj->job.ctrl) << 7 | (uint32_t)fp_wide_lds(*dj) << 8 |
            (uint32_t)l1_full(*dj) << 9 | (uint32_t)svtme_l0_full(dj) << 10 |
-           (uint32_t)((dj->paths & SVTME_PATH_SPLIT_PASS) != 0) << 11;
+           (uint32_t)((dj->paths & SVTME_PATH_SPLIT_PASS) != 0) << 11 | (uint32_t)(hme_waves(*dj) == 3) << 12;
 }
 
 static DevBatch make_batch(const DevJob *d_jobs, const DevJob *h, uint32_t n, uint32_t (*units)(const DevJob &)) {
@@ -4932,19 +5002,21 @@ static DevBatch make_batch(const DevJob *d_jobs, const DevJob *h, uint32_t n, ui
 // themselves (hipExtLaunchKernelGGL: no extra packets, no gaps); *mask gets
 // bit k for every stage launched. With the real-time tune on the split path,
 // stage A spans both stage-A rounds and the k_stage_d<true> between them.
-#define SVTME_LAUNCH(K, grid, k, ...)                                                                               \
+#define SVTME_LAUNCH_NT(K, grid, nt, k, ...)                                                                        \
     do {                                                                                                           \
         if (ev) {                                                                                                  \
-            hipExtLaunchKernelGGL(K, grid, dim3(256), 0, s, ev[2 * (k)], ev[2 * (k) + 1], 0, __VA_ARGS__);           \
+            hipExtLaunchKernelGGL(K, grid, dim3(nt), 0, s, ev[2 * (k)], ev[2 * (k) + 1], 0, __VA_ARGS__);            \
             *mask |= 1u << (k);                                                                                    \
         } else                                                                                                     \
-            hipLaunchKernelGGL(K, grid, dim3(256), 0, s, __VA_ARGS__);                                             \
+            hipLaunchKernelGGL(K, grid, dim3(nt), 0, s, __VA_ARGS__);                                              \
     } while (0)
+#define SVTME_LAUNCH(K, grid, k, ...) SVTME_LAUNCH_NT(K, grid, 256, k, __VA_ARGS__)
 
 extern "C" hipError_t svtme_prime_stages(void) { // (see svtme_prime_pyramid): every kernel a job can launch
     const void *k[] = {
         (const void *)svtme::k_hme<true, true, true, false>,   (const void *)svtme::k_hme<true, true, true, true>,
         (const void *)svtme::k_hme<false, true, true, false>,  (const void *)svtme::k_hme<true, true, false, false>,
+        (const void *)svtme::k_hme<true, true, true, false, 3>, (const void *)svtme::k_hme<true, true, false, false, 3>,
         (const void *)svtme::k_stage_a<false>,                 (const void *)svtme::k_stage_a<true>,
         (const void *)svtme::k_stage_d<false>,                 (const void *)svtme::k_stage_d<true>,
         (const void *)svtme::k_stage_b<false>,                 (const void *)svtme::k_stage_b<true>,
@@ -4984,7 +5056,11 @@ extern "C" hipError_t svtme_launch_stages(const DevJob *d_jobs, const DevJob *h_
             SVTME_LAUNCH((svtme::k_hme<FP, SUB, K32, false>), dim3(bd.total), 0, bd);                              \
     } while (0)
     if (hme_fused(h0) && h0.parts == 1 && !(h0.paths & SVTME_PATH_SPLIT_PASS)) {
-        if (full && k32)
+        if (hme_waves(h0) == 3 && k32) // (svtme_hme_waves: sub-sampled rows, no real-time reduction)
+            SVTME_LAUNCH_NT((svtme::k_hme<true, true, true, false, 3>), dim3(bd.total), 192, 0, bd);
+        else if (hme_waves(h0) == 3)
+            SVTME_LAUNCH_NT((svtme::k_hme<true, true, false, false, 3>), dim3(bd.total), 192, 0, bd);
+        else if (full && k32)
             SVTME_HME(true, false, true);
         else if (full)
             SVTME_HME(true, false, false);

@@ -28,6 +28,7 @@ SUB_SAD_SEARCH, FULL_SAD_SEARCH = 0, 1
 ME_MCTF, ME_OPEN_LOOP = 1, 3  # EbMeType (me_context.h:44-51)
 # kernel-path selection bits (include/svtme.h SVTME_PATH_*)
 PATH_NO_FUSED_HME, PATH_NO_L1_FULL, PATH_NO_L0_FULL, PATH_NO_FP_WIDE, PATH_SPLIT_PASS = 1, 2, 4, 8, 16
+PATH_NO_A1_GATE, PATH_HME_4WAVES = 32, 64
 # EbInputResolution (definitions.h:2079-2085)
 RES_240P, RES_360P, RES_480P, RES_720P, RES_1080P, RES_4K, RES_8K = range(7)
 
