@@ -577,6 +577,47 @@ svtme_status svtme_tf_subpel(svtme_ctx *ctx, uint64_t centre_picture_number, con
                              uint32_t n, uint32_t width, uint32_t height, const svtme_tf_subpel_controls *controls,
                              const svtme_ref_record *records, svtme_tf_subpel_sb *out);
 
+/* ---------------------------------------------------------------------------
+ * Temporal filtering: the step after the sub-pel refinement
+ * (temporal_filtering.c:3196-3390): the final inter prediction of every block
+ * (MULTITAP_SHARP), the 32x32 errors of the 64x64 branches, the per-16x16
+ * filter weights (svt_av1_apply_temporal_filter_planewise_medium_c, luma), the
+ * accumulation over the window and the normalisation
+ * (svt_aom_get_final_filtered_pixels_c). Luma, 8-bit,
+ * tf_ctrls.use_zz_based_filter == 0.
+ * ------------------------------------------------------------------------- */
+typedef struct svtme_tf_filter_controls {
+    uint32_t tf_decay_factor_fp16; /* MeContext.tf_decay_factor_fp16[C_Y], any value */
+    uint16_t tf_mv_dist_th;        /* MeContext.tf_mv_dist_th, 0..32767 (the reference sets 64..450) */
+    uint8_t sub_sampling_shift;    /* tf_ctrls.sub_sampling_shift, 0..1 */
+    uint8_t pad;
+} svtme_tf_filter_controls; /* 8 bytes */
+#ifdef __cplusplus
+static_assert(sizeof(svtme_tf_filter_controls) == 8, "svtme_tf_filter layout");
+#else
+_Static_assert(sizeof(svtme_tf_filter_controls) == 8, "svtme_tf_filter layout");
+#endif
+
+/* The filtered luma of the centre picture from n references (1 ..
+ * SVTME_MAX_BATCH_JOBS, the references the caller kept) of one window, on lane 0's
+ * stream. All pictures are resident and width x height (the aligned size the other
+ * TF calls take). `subpel` holds n x svtme_sb_total(width, height) results of
+ * svtme_tf_subpel in host memory, in the order of ref_picture_numbers. `out`
+ * receives every pixel x < width, y < height of what
+ * svt_aom_get_final_filtered_pixels_c leaves in the centre picture, rows out_stride
+ * bytes apart; bytes at x >= width are not written. `err32_out` is NULL or receives
+ * n x SBs x 4 values: the 32x32 block error the reference holds when it filters
+ * that quadrant (64x64 branches: convert_64x64_info_to_32x32_info's variance of the
+ * final prediction; SVTME_TFSP_32: the sub-pel stage's error). The resident centre
+ * picture is not modified. Synchronous; returns SVTME_ERR_BAD_PARAMETER before any
+ * GPU work for a NULL ctx / ref_picture_numbers / controls / subpel / out, n out of
+ * range, out_stride < width, a control above its range, a subpel[..].branch above
+ * 2, a picture that is not resident or has another size. */
+svtme_status svtme_tf_filter(svtme_ctx *ctx, uint64_t centre_picture_number, const uint64_t *ref_picture_numbers,
+                             uint32_t n, uint32_t width, uint32_t height, const svtme_tf_filter_controls *controls,
+                             const svtme_tf_subpel_sb *subpel, uint8_t *out, uint32_t out_stride,
+                             uint32_t *err32_out);
+
 /* Number of 64x64 SBs of a width x height picture, and R for a job. */
 uint32_t svtme_sb_total(uint32_t width, uint32_t height);
 uint32_t svtme_job_ref_slots(const svtme_job *job);

@@ -50,6 +50,11 @@ extern "C" hipError_t svtme_prime_tfsp(void);
 extern "C" hipError_t svtme_launch_tfsp(const DevPlane *cen, const DevPlane *ref, uint32_t n, uint32_t width,
                                         uint32_t height, const svtme_tf_subpel_controls *ctl,
                                         const svtme_ref_record *d_rec, svtme_tf_subpel_sb *d_out, hipStream_t s);
+extern "C" hipError_t svtme_prime_tff(void);
+extern "C" hipError_t svtme_launch_tff(const DevPlane *cen, const DevPlane *ref, uint32_t n, uint32_t width,
+                                       uint32_t height, const svtme_tf_filter_controls *ctl,
+                                       const svtme_tf_subpel_sb *d_sub, uint8_t *d_tile, uint32_t *d_wgt,
+                                       uint32_t *d_e32, uint8_t *d_plane, hipStream_t s);
 extern "C" void svtme_stage_a_list(const svtme_job *job, uint8_t *list, uint32_t *count);
 extern "C" void svtme_stage_b_list(const svtme_job *job, uint8_t *list, uint32_t *count);
 extern "C" void svtme_stage_a1_list(const svtme_job *job, uint8_t *list, uint32_t *count);
@@ -172,6 +177,8 @@ struct svtme_ctx {
     size_t dg_cap = 0;
     void *d_tfsp    = nullptr; // svtme_tf_subpel: n x SBs records | n x SBs results
     size_t tfsp_cap = 0;
+    void *d_tff     = nullptr; // svtme_tf_filter: results of the sub-pel stage | tiles | weights | errors | plane
+    size_t tff_cap  = 0;
     uint32_t last_count = 0, last_R = 0;
     bool last_has_sb    = false;
     // job tables: a ring of device slots of SVTME_MAX_BATCH DevJobs, copied from
@@ -235,7 +242,7 @@ extern "C" svtme_status svtme_ctx_create(int device, svtme_ctx **out) {
     // the code objects of the kernels, loaded now rather than at a first job's launches
     if ((e = svtme_prime_pyramid()) != hipSuccess || (e = svtme_prime_pack()) != hipSuccess ||
         (e = svtme_prime_stages()) != hipSuccess || (e = svtme_prime_dg()) != hipSuccess ||
-        (e = svtme_prime_tfsp()) != hipSuccess) {
+        (e = svtme_prime_tfsp()) != hipSuccess || (e = svtme_prime_tff()) != hipSuccess) {
         (void)hipStreamDestroy(c->stream);
         delete c;
         return fail(SVTME_ERR_UNDEFINED, "svtme_ctx_create: loading the kernels: %s", hipGetErrorString(e));
@@ -310,6 +317,8 @@ extern "C" void svtme_ctx_destroy(svtme_ctx *c) {
         (void)hipFree(c->d_dg);
     if (c->d_tfsp)
         (void)hipFree(c->d_tfsp);
+    if (c->d_tff)
+        (void)hipFree(c->d_tff);
     for (auto &set : c->tev)
         for (auto &e : set)
             if (e)
@@ -1708,6 +1717,79 @@ extern "C" svtme_status svtme_tf_subpel(svtme_ctx *c, uint64_t centre_picture_nu
     HIP_TRY(hipEventRecord(done, L.s));
     for (uint32_t k = 0; k <= n; k++) pb[k]->used[0] = done;
     HIP_TRY(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, L.s));
+    HIP_TRY(hipStreamSynchronize(L.s));
+    return SVTME_OK;
+}
+
+// ----------------------------------------------------------------------------
+// Temporal filtering's luma prediction and weighting (svtme_tff.hip). Held under
+// the context lock from the launch to the copy-out, as svtme_tf_subpel is.
+// ----------------------------------------------------------------------------
+extern "C" svtme_status svtme_tf_filter(svtme_ctx *c, uint64_t centre_picture_number,
+                                        const uint64_t *ref_picture_numbers, uint32_t n, uint32_t width,
+                                        uint32_t height, const svtme_tf_filter_controls *ctl,
+                                        const svtme_tf_subpel_sb *subpel, uint8_t *out, uint32_t out_stride,
+                                        uint32_t *err32_out) {
+    if (!c || !ref_picture_numbers || !ctl || !subpel || !out)
+        return fail(SVTME_ERR_BAD_PARAMETER, "svtme_tf_filter: null ctx, ref_picture_numbers, controls, subpel or out");
+    if (n < 1 || n > SVTME_MAX_BATCH_JOBS)
+        return fail(SVTME_ERR_BAD_PARAMETER, "svtme_tf_filter: %u references (1..%d)", n, SVTME_MAX_BATCH_JOBS);
+    if (ctl->tf_mv_dist_th > 32767 || ctl->sub_sampling_shift > 1)
+        return fail(SVTME_ERR_BAD_PARAMETER,
+                    "svtme_tf_filter: controls out of range: tf_mv_dist_th %u (0..32767), sub_sampling_shift %u (0..1)",
+                    ctl->tf_mv_dist_th, ctl->sub_sampling_shift);
+    if (!width || !height)
+        return fail(SVTME_ERR_BAD_PARAMETER, "svtme_tf_filter: %ux%u picture", width, height);
+    if (out_stride < width)
+        return fail(SVTME_ERR_BAD_PARAMETER, "svtme_tf_filter: out_stride %u under the width %u", out_stride, width);
+    const uint32_t W = svtme_align8_u(width), H = svtme_align8_u(height);
+    const uint32_t sbs = svtme_sb_total(W, H);
+    for (size_t k = 0; k < (size_t)n * sbs; k++)
+        if (subpel[k].branch > SVTME_TFSP_32)
+            return fail(SVTME_ERR_BAD_PARAMETER, "svtme_tf_filter: subpel[%zu].branch is %u (0..2)", k, subpel[k].branch);
+    std::lock_guard<std::mutex> lk(c->mu);
+    PicBuf *pb[SVTME_MAX_BATCH_JOBS + 1];
+    for (uint32_t k = 0; k <= n; k++) {
+        const uint64_t pn = k ? ref_picture_numbers[k - 1] : centre_picture_number;
+        auto it           = c->pics.find(pn);
+        if (it == c->pics.end())
+            return fail(SVTME_ERR_BAD_PARAMETER, "svtme_tf_filter: picture %llu is not resident", (unsigned long long)pn);
+        pb[k] = &it->second;
+        if (pb[k]->W != W || pb[k]->H != H)
+            return fail(SVTME_ERR_BAD_PARAMETER, "svtme_tf_filter: picture %llu is %ux%u, the window %ux%u",
+                        (unsigned long long)pn, pb[k]->W, pb[k]->H, W, H);
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    // results of the sub-pel stage | tiles | weights | errors | the plane, whole SBs
+    const size_t units = (size_t)n * sbs, pstride = (size_t)((W + 63) / 64) * 64;
+    const size_t sub_bytes = sizeof(svtme_tf_subpel_sb) * units, tile_bytes = 4096 * units, wgt_bytes = 64 * units,
+                 e32_bytes = 16 * units, plane_bytes = 4096 * (size_t)sbs;
+    svtme_status st = ensure_buf(&c->d_tff, &c->tff_cap, sub_bytes + tile_bytes + wgt_bytes + e32_bytes + plane_bytes);
+    if (st)
+        return st;
+    DevPlane ref[SVTME_MAX_BATCH_JOBS];
+    for (uint32_t k = 0; k <= n; k++) {
+        if ((st = join_upload(c, *pb[k], 0)))
+            return st;
+        if (k)
+            ref[k - 1] = pb[k]->pyr.lv[0];
+    }
+    Lane &L                   = c->lanes[0];
+    uint8_t *base             = (uint8_t *)c->d_tff;
+    svtme_tf_subpel_sb *d_sub = (svtme_tf_subpel_sb *)base; // 704 bytes each: the sections stay 16-byte aligned
+    uint8_t *d_tile           = base + sub_bytes;
+    uint32_t *d_wgt           = (uint32_t *)(d_tile + tile_bytes);
+    uint32_t *d_e32           = (uint32_t *)(d_tile + tile_bytes + wgt_bytes);
+    uint8_t *d_plane          = d_tile + tile_bytes + wgt_bytes + e32_bytes;
+    HIP_TRY(hipMemcpyAsync(d_sub, subpel, sub_bytes, hipMemcpyHostToDevice, L.s));
+    HIP_TRY(svtme_launch_tff(&pb[0]->pyr.lv[0], ref, n, W, H, ctl, d_sub, d_tile, d_wgt, d_e32, d_plane, L.s));
+    hipEvent_t done = L.ev[L.ev_next];
+    L.ev_next       = (L.ev_next + 1) % Lane::kEv;
+    HIP_TRY(hipEventRecord(done, L.s));
+    for (uint32_t k = 0; k <= n; k++) pb[k]->used[0] = done;
+    HIP_TRY(hipMemcpy2DAsync(out, out_stride, d_plane, pstride, width, height, hipMemcpyDeviceToHost, L.s));
+    if (err32_out)
+        HIP_TRY(hipMemcpyAsync(err32_out, d_e32, e32_bytes, hipMemcpyDeviceToHost, L.s));
     HIP_TRY(hipStreamSynchronize(L.s));
     return SVTME_OK;
 }

@@ -263,6 +263,19 @@ class TfSubpelControls(C.Structure):
         return {name: int(getattr(self, name)) for name, _ in self._fields_}
 
 
+class TfFilterControls(C.Structure):
+    """svtme_tf_filter_controls: the MeContext / tf_ctrls fields the filter reads."""
+    _fields_ = [("tf_decay_factor_fp16", C.c_uint32), ("tf_mv_dist_th", C.c_uint16),
+                ("sub_sampling_shift", C.c_uint8), ("pad", C.c_uint8)]
+
+    @staticmethod
+    def from_dict(d: dict) -> "TfFilterControls":
+        return TfFilterControls(**{k: int(v) for k, v in d.items()})
+
+    def as_dict(self) -> dict:
+        return {name: int(getattr(self, name)) for name, _ in self._fields_ if name != "pad"}
+
+
 TAIL_BYTES = 24  # svtme_record_tail: the last 24 bytes of svtme_ref_record
 
 
@@ -710,6 +723,9 @@ def _job_api_protos(lib):
         _proto(lib, "svtme_tf_subpel", "argtypes", [vp, C.c_uint64, C.POINTER(C.c_uint64), C.c_uint32, C.c_uint32,
                                                     C.c_uint32, C.POINTER(TfSubpelControls), vp, vp])
         _proto(lib, "svtme_tf_subpel", "restype", C.c_int32)
+        _proto(lib, "svtme_tf_filter", "argtypes", [vp, C.c_uint64, C.POINTER(C.c_uint64), C.c_uint32, C.c_uint32,
+                                                    C.c_uint32, C.POINTER(TfFilterControls), vp, vp, C.c_uint32, vp])
+        _proto(lib, "svtme_tf_filter", "restype", C.c_int32)
         lib._svtme_protos = True
     return lib
 
@@ -968,6 +984,26 @@ class GpuME:
         self._check(self.lib.svtme_tf_subpel(self.ctx, int(centre), arr, n, width, height, C.byref(controls),
                                              records.ctypes.data, out.ctypes.data), "svtme_tf_subpel")
         return out
+
+    def tf_filter(self, centre: int, refs, width: int, height: int, controls: TfFilterControls,
+                  subpel: np.ndarray, with_err32: bool = True, out_stride: int = None):
+        """svtme_tf_filter: the temporally filtered luma of the centre picture from the references
+        `refs` (picture numbers) and the results subpel[len(refs), SBs] of tf_subpel ->
+        (plane [height, width] u8, err32 [len(refs), SBs, 4] u32 or None). With out_stride the plane
+        is a view of rows that far apart."""
+        n = len(refs)
+        sbs = sb_total(align8(width), align8(height))
+        subpel = np.ascontiguousarray(subpel, TF_SUBPEL_SB_DTYPE)
+        if subpel.size != n * sbs:
+            raise ValueError(f"{subpel.size} sub-pel results for {n} references x {sbs} SBs")
+        arr = (C.c_uint64 * max(n, 1))(*[int(r) for r in refs])
+        stride = width if out_stride is None else out_stride
+        buf = np.zeros((height, stride), np.uint8)
+        err32 = np.zeros((n, sbs, 4), np.uint32) if with_err32 else None
+        self._check(self.lib.svtme_tf_filter(self.ctx, int(centre), arr, n, width, height, C.byref(controls),
+                                             subpel.ctypes.data, buf.ctypes.data, stride,
+                                             err32.ctypes.data if with_err32 else None), "svtme_tf_filter")
+        return buf[:, :width], err32
 
     def device_records(self):
         n = C.c_uint64()
