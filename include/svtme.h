@@ -618,6 +618,61 @@ svtme_status svtme_tf_filter(svtme_ctx *ctx, uint64_t centre_picture_number, con
                              const svtme_tf_subpel_sb *subpel, uint8_t *out, uint32_t out_stride,
                              uint32_t *err32_out);
 
+/* ---------------------------------------------------------------------------
+ * Temporal filtering: one window in one call, resident to resident. The
+ * window's TF-ME jobs, svtme_tf_subpel and svtme_tf_filter chained on lane 0's
+ * stream through device memory, and the filtered luma left as a resident
+ * picture (what pad_and_decimate_filtered_pic leaves in the encoder,
+ * temporal_filtering.c:3895-3934). Nothing crosses to the host unless asked for.
+ * ------------------------------------------------------------------------- */
+/* Host copies of the window's results; every pointer may be NULL. */
+typedef struct svtme_tf_window_out {
+    uint8_t *plane;            /* filtered luma, x < src_width, y < src_height, after the re-pad */
+    uint32_t plane_stride;     /* bytes between its rows, >= src_width; bytes at x >= src_width are not written */
+    uint32_t pad;
+    svtme_ref_record *records; /* n x SBs: slot 0 of each TF-ME job (what svtme_tf_subpel takes) */
+    svtme_tf_subpel_sb *subpel; /* n x SBs: what svtme_tf_subpel returns */
+    uint32_t *err32;           /* n x SBs x 4: what svtme_tf_filter returns */
+} svtme_tf_window_out;         /* 40 bytes */
+#ifdef __cplusplus
+static_assert(sizeof(svtme_tf_window_out) == 40, "svtme_tf_window layout");
+#else
+_Static_assert(sizeof(svtme_tf_window_out) == 40, "svtme_tf_window layout");
+#endif
+
+/* `jobs` are the window's n TF-ME jobs (1 .. SVTME_MAX_BATCH_JOBS) as
+ * svtme_submit_pictures_packed_async takes them: me_type SVTME_ME_MCTF, one list
+ * with one reference (job k's is ref_picture_number[0][0]), all with the same
+ * picture_number (the centre) and the same width x height, each over the whole
+ * picture (sb_begin 0, sb_count 0 or every SB). src_width x src_height is the size
+ * the centre picture was uploaded with; aligned to 8 it is the jobs' size.
+ *
+ * The jobs run as one batch and write their records where the sub-pel stage reads
+ * them; its results stay where the filter reads them; the normalisation writes
+ * level 0 of the picture out_picture_number (the window's aligned size). There the
+ * samples at x >= src_width or y >= src_height are re-padded from the last true
+ * column and row, the margins written and levels 1 and 2 decimated, as an upload of
+ * the src_width x src_height filtered plane would leave them. out_picture_number
+ * may be the centre's number: the picture is replaced in place, after work queued
+ * earlier on any lane that reads it. It may not be one of the references. Any other
+ * number leaves the centre picture as it was. Later jobs on any lane that read the
+ * result picture are ordered after the window on the GPU.
+ *
+ * With `out` NULL or every pointer of it NULL the call returns once the work is
+ * queued (svtme_sync, or any later synchronous call on the context, covers it);
+ * otherwise it returns when the requested copies are written.
+ *
+ * Returns SVTME_ERR_BAD_PARAMETER before any GPU work for a NULL ctx / jobs /
+ * controls, n out of range, a job that is not SVTME_ME_MCTF, has more than one
+ * reference, another centre, another size or covers part of the picture, src_* that
+ * do not align to the jobs' size, plane set with plane_stride < src_width, a control
+ * above the ranges of svtme_tf_subpel / svtme_tf_filter, a picture that is not
+ * resident or has another size, out_picture_number among the references. */
+svtme_status svtme_tf_window(svtme_ctx *ctx, const svtme_job *jobs, uint32_t n, uint32_t src_width,
+                             uint32_t src_height, const svtme_tf_subpel_controls *subpel_controls,
+                             const svtme_tf_filter_controls *filter_controls, uint64_t out_picture_number,
+                             const svtme_tf_window_out *out);
+
 /* Number of 64x64 SBs of a width x height picture, and R for a job. */
 uint32_t svtme_sb_total(uint32_t width, uint32_t height);
 uint32_t svtme_job_ref_slots(const svtme_job *job);

@@ -55,6 +55,10 @@ extern "C" hipError_t svtme_launch_tff(const DevPlane *cen, const DevPlane *ref,
                                        uint32_t height, const svtme_tf_filter_controls *ctl,
                                        const svtme_tf_subpel_sb *d_sub, uint8_t *d_tile, uint32_t *d_wgt,
                                        uint32_t *d_e32, uint8_t *d_plane, hipStream_t s);
+extern "C" hipError_t svtme_launch_tff_pic(const DevPlane *cen, const DevPlane *ref, uint32_t n, uint32_t width,
+                                           uint32_t height, const svtme_tf_filter_controls *ctl,
+                                           const svtme_tf_subpel_sb *d_sub, uint8_t *d_tile, uint32_t *d_wgt,
+                                           uint32_t *d_e32, const DevPlane *dst, hipStream_t s);
 extern "C" void svtme_stage_a_list(const svtme_job *job, uint8_t *list, uint32_t *count);
 extern "C" void svtme_stage_b_list(const svtme_job *job, uint8_t *list, uint32_t *count);
 extern "C" void svtme_stage_a1_list(const svtme_job *job, uint8_t *list, uint32_t *count);
@@ -1663,6 +1667,15 @@ extern "C" svtme_status svtme_dg_detect(svtme_ctx *c, const svtme_dg_pair *pairs
 // Temporal filtering's sub-pel refinement (svtme_tfsp.hip). Held under the context
 // lock from the launch to the copy-out, as svtme_dg_detect is.
 // ----------------------------------------------------------------------------
+// the ranges of the two stages' controls (svtme_tf_subpel, svtme_tf_filter, svtme_tf_window)
+static bool tfsp_controls_ok(const svtme_tf_subpel_controls *ctl) {
+    return ctl->half_pel_mode <= 3 && ctl->quarter_pel_mode <= 3 && ctl->eight_pel_mode <= 1 && ctl->use_2tap <= 1 &&
+           ctl->sub_sampling_shift <= 1 && ctl->enable_8x8_pred <= 1;
+}
+static bool tff_controls_ok(const svtme_tf_filter_controls *ctl) {
+    return ctl->tf_mv_dist_th <= 32767 && ctl->sub_sampling_shift <= 1;
+}
+
 extern "C" svtme_status svtme_tf_subpel(svtme_ctx *c, uint64_t centre_picture_number,
                                         const uint64_t *ref_picture_numbers, uint32_t n, uint32_t width,
                                         uint32_t height, const svtme_tf_subpel_controls *ctl,
@@ -1671,8 +1684,7 @@ extern "C" svtme_status svtme_tf_subpel(svtme_ctx *c, uint64_t centre_picture_nu
         return fail(SVTME_ERR_BAD_PARAMETER, "svtme_tf_subpel: null ctx, ref_picture_numbers, controls, records or out");
     if (n < 1 || n > SVTME_MAX_BATCH_JOBS)
         return fail(SVTME_ERR_BAD_PARAMETER, "svtme_tf_subpel: %u references (1..%d)", n, SVTME_MAX_BATCH_JOBS);
-    if (ctl->half_pel_mode > 3 || ctl->quarter_pel_mode > 3 || ctl->eight_pel_mode > 1 || ctl->use_2tap > 1 ||
-        ctl->sub_sampling_shift > 1 || ctl->enable_8x8_pred > 1)
+    if (!tfsp_controls_ok(ctl))
         return fail(SVTME_ERR_BAD_PARAMETER,
                     "svtme_tf_subpel: controls out of range: half %u quarter %u (0..3), eighth %u, use_2tap %u, "
                     "sub_sampling_shift %u, enable_8x8_pred %u (0..1)",
@@ -1734,7 +1746,7 @@ extern "C" svtme_status svtme_tf_filter(svtme_ctx *c, uint64_t centre_picture_nu
         return fail(SVTME_ERR_BAD_PARAMETER, "svtme_tf_filter: null ctx, ref_picture_numbers, controls, subpel or out");
     if (n < 1 || n > SVTME_MAX_BATCH_JOBS)
         return fail(SVTME_ERR_BAD_PARAMETER, "svtme_tf_filter: %u references (1..%d)", n, SVTME_MAX_BATCH_JOBS);
-    if (ctl->tf_mv_dist_th > 32767 || ctl->sub_sampling_shift > 1)
+    if (!tff_controls_ok(ctl))
         return fail(SVTME_ERR_BAD_PARAMETER,
                     "svtme_tf_filter: controls out of range: tf_mv_dist_th %u (0..32767), sub_sampling_shift %u (0..1)",
                     ctl->tf_mv_dist_th, ctl->sub_sampling_shift);
@@ -1790,6 +1802,139 @@ extern "C" svtme_status svtme_tf_filter(svtme_ctx *c, uint64_t centre_picture_nu
     HIP_TRY(hipMemcpy2DAsync(out, out_stride, d_plane, pstride, width, height, hipMemcpyDeviceToHost, L.s));
     if (err32_out)
         HIP_TRY(hipMemcpyAsync(err32_out, d_e32, e32_bytes, hipMemcpyDeviceToHost, L.s));
+    HIP_TRY(hipStreamSynchronize(L.s));
+    return SVTME_OK;
+}
+
+// ----------------------------------------------------------------------------
+// One temporal-filtering window, resident to resident: the TF-ME batch, k_tfsp,
+// k_tff_pred and the normalisation into the result picture, chained by lane 0's
+// stream through the two stages' scratch. Held under the context lock from the
+// first launch to the last copy.
+// ----------------------------------------------------------------------------
+extern "C" svtme_status svtme_tf_window(svtme_ctx *c, const svtme_job *jobs, uint32_t n, uint32_t src_width,
+                                        uint32_t src_height, const svtme_tf_subpel_controls *sp_ctl,
+                                        const svtme_tf_filter_controls *f_ctl, uint64_t out_pn,
+                                        const svtme_tf_window_out *out) {
+    if (!c || !jobs || !sp_ctl || !f_ctl)
+        return fail(SVTME_ERR_BAD_PARAMETER, "svtme_tf_window: null ctx, jobs, subpel_controls or filter_controls");
+    if (n < 1 || n > SVTME_MAX_BATCH_JOBS)
+        return fail(SVTME_ERR_BAD_PARAMETER, "svtme_tf_window: %u jobs (1..%d)", n, SVTME_MAX_BATCH_JOBS);
+    const uint32_t W = jobs[0].width, H = jobs[0].height;
+    if (!W || !H || (W & 7) || (H & 7) || W > 16384 || H > 16384)
+        return fail(SVTME_ERR_BAD_PARAMETER, "svtme_tf_window: job size %ux%u must be a non-zero multiple of 8, "
+                                             "16384 at the most", W, H);
+    const uint32_t sbs = svtme_sb_total(W, H);
+    for (uint32_t k = 0; k < n; k++) {
+        const svtme_job &j = jobs[k];
+        if (j.me_type != SVTME_ME_MCTF || j.num_lists != 1 || j.num_refs[0] != 1)
+            return fail(SVTME_ERR_BAD_PARAMETER,
+                        "svtme_tf_window: job %u: me_type %u, %u lists, %u references (SVTME_ME_MCTF, one list, one "
+                        "reference)", k, j.me_type, j.num_lists, j.num_refs[0]);
+        if (j.picture_number != jobs[0].picture_number)
+            return fail(SVTME_ERR_BAD_PARAMETER, "svtme_tf_window: job %u's centre is picture %llu, job 0's %llu", k,
+                        (unsigned long long)j.picture_number, (unsigned long long)jobs[0].picture_number);
+        if (j.width != W || j.height != H)
+            return fail(SVTME_ERR_BAD_PARAMETER, "svtme_tf_window: job %u is %ux%u, job 0 %ux%u", k, j.width, j.height,
+                        W, H);
+        if (j.sb_begin != 0 || (j.sb_count != 0 && j.sb_count != sbs))
+            return fail(SVTME_ERR_BAD_PARAMETER, "svtme_tf_window: job %u covers SBs [%u, %u) of %u: the whole picture "
+                                                 "only", k, j.sb_begin, j.sb_begin + j.sb_count, sbs);
+    }
+    if (!src_width || !src_height || svtme_align8_u(src_width) != W || svtme_align8_u(src_height) != H)
+        return fail(SVTME_ERR_BAD_PARAMETER, "svtme_tf_window: source size %ux%u does not align to the jobs' %ux%u",
+                    src_width, src_height, W, H);
+    if (out && out->plane && out->plane_stride < src_width)
+        return fail(SVTME_ERR_BAD_PARAMETER, "svtme_tf_window: plane_stride %u under the width %u", out->plane_stride,
+                    src_width);
+    if (!tfsp_controls_ok(sp_ctl))
+        return fail(SVTME_ERR_BAD_PARAMETER,
+                    "svtme_tf_window: sub-pel controls out of range: half %u quarter %u (0..3), eighth %u, use_2tap %u, "
+                    "sub_sampling_shift %u, enable_8x8_pred %u (0..1)",
+                    sp_ctl->half_pel_mode, sp_ctl->quarter_pel_mode, sp_ctl->eight_pel_mode, sp_ctl->use_2tap,
+                    sp_ctl->sub_sampling_shift, sp_ctl->enable_8x8_pred);
+    if (!tff_controls_ok(f_ctl))
+        return fail(SVTME_ERR_BAD_PARAMETER,
+                    "svtme_tf_window: filter controls out of range: tf_mv_dist_th %u (0..32767), sub_sampling_shift %u "
+                    "(0..1)", f_ctl->tf_mv_dist_th, f_ctl->sub_sampling_shift);
+    const uint64_t cen_pn = jobs[0].picture_number;
+    for (uint32_t k = 0; k < n; k++)
+        if (jobs[k].ref_picture_number[0][0] == out_pn)
+            return fail(SVTME_ERR_BAD_PARAMETER, "svtme_tf_window: the result picture %llu is job %u's reference",
+                        (unsigned long long)out_pn, k);
+    std::lock_guard<std::mutex> lk(c->mu);
+    for (uint32_t k = 0; k <= n; k++) { // (the batch checks the same; here before the result picture is made)
+        const uint64_t pn = k ? jobs[k - 1].ref_picture_number[0][0] : cen_pn;
+        auto it           = c->pics.find(pn);
+        if (it == c->pics.end())
+            return fail(SVTME_ERR_BAD_PARAMETER, "svtme_tf_window: picture %llu is not resident", (unsigned long long)pn);
+        if (it->second.W != W || it->second.H != H)
+            return fail(SVTME_ERR_BAD_PARAMETER, "svtme_tf_window: picture %llu is %ux%u, the window %ux%u",
+                        (unsigned long long)pn, it->second.W, it->second.H, W, H);
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    // the sub-pel scratch holds the records (its results go to the filter's scratch), the filter's
+    // scratch the results of the sub-pel stage | tiles | weights | errors (no dense plane)
+    const size_t units = (size_t)n * sbs;
+    const size_t rec_bytes = sizeof(svtme_ref_record) * units, sub_bytes = sizeof(svtme_tf_subpel_sb) * units,
+                 tile_bytes = 4096 * units, wgt_bytes = 64 * units, e32_bytes = 16 * units;
+    svtme_status st;
+    if ((st = ensure_buf(&c->d_tfsp, &c->tfsp_cap, rec_bytes)) ||
+        (st = ensure_buf(&c->d_tff, &c->tff_cap, sub_bytes + tile_bytes + wgt_bytes + e32_bytes)))
+        return st;
+    svtme_ref_record *d_rec   = (svtme_ref_record *)c->d_tfsp;
+    uint8_t *base             = (uint8_t *)c->d_tff;
+    svtme_tf_subpel_sb *d_sub = (svtme_tf_subpel_sb *)base;
+    uint8_t *d_tile           = base + sub_bytes;
+    uint32_t *d_wgt           = (uint32_t *)(d_tile + tile_bytes);
+    uint32_t *d_e32           = (uint32_t *)(d_tile + tile_bytes + wgt_bytes);
+    // the TF-ME jobs: one batch, job k's records (R = 1) at d_rec + k x SBs, the array k_tfsp reads
+    svtme_ref_record *recs_of[SVTME_MAX_BATCH_JOBS];
+    for (uint32_t k = 0; k < n; k++) recs_of[k] = d_rec + (size_t)k * sbs;
+    if ((st = submit_batch_locked(c, jobs, n, recs_of, nullptr, false, 0)))
+        return st;
+    // the result picture (a new number: a buffer of the pool; std::map keeps the others where they are)
+    PicBuf *po;
+    if ((st = alloc_pic(c, out_pn, W, H, &po)))
+        return st;
+    PicBuf *pb[SVTME_MAX_BATCH_JOBS + 1];
+    DevPlane ref[SVTME_MAX_BATCH_JOBS];
+    for (uint32_t k = 0; k <= n; k++) { // (resident and joined to lane 0: the batch saw to both)
+        pb[k] = &c->pics.find(k ? jobs[k - 1].ref_picture_number[0][0] : cen_pn)->second;
+        if (k)
+            ref[k - 1] = pb[k]->pyr.lv[0];
+    }
+    Lane &L = c->lanes[0];
+    // its old planes, if it had any: an upload still running, readers queued on the other lanes
+    if ((st = join_upload(c, *po, 0)) || (st = after_readers(c, *po, L.s)))
+        return st;
+    HIP_TRY(svtme_launch_tfsp(&pb[0]->pyr.lv[0], ref, n, W, H, sp_ctl, d_rec, d_sub, L.s));
+    HIP_TRY(svtme_launch_tff_pic(&pb[0]->pyr.lv[0], ref, n, W, H, f_ctl, d_sub, d_tile, d_wgt, d_e32, &po->pyr.lv[0],
+                                 L.s));
+    // the sub-8 re-pad and the margins from the plane's own interior, then levels 1 and 2
+    if ((st = build_pyramid(c, po, po->pyr.lv[0].base, (uint32_t)po->pyr.lv[0].stride, src_width, src_height, 0, L.s)))
+        return st;
+    hipEvent_t done = L.ev[L.ev_next];
+    L.ev_next       = (L.ev_next + 1) % Lane::kEv;
+    HIP_TRY(hipEventRecord(done, L.s));
+    for (uint32_t k = 0; k <= n; k++) pb[k]->used[0] = done;
+    po->used[0] = done; // a later upload under its number waits for the window
+    // the other lanes' later readers wait for the window as they do for an asynchronous upload
+    if (!po->ready)
+        HIP_TRY(hipEventCreateWithFlags(&po->ready, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(po->ready, L.s));
+    po->pending = ((1u << SVTME_LANES) - 1u) & ~1u;
+    if (!out || (!out->plane && !out->records && !out->subpel && !out->err32))
+        return SVTME_OK;
+    if (out->records)
+        HIP_TRY(hipMemcpyAsync(out->records, d_rec, rec_bytes, hipMemcpyDeviceToHost, L.s));
+    if (out->subpel)
+        HIP_TRY(hipMemcpyAsync(out->subpel, d_sub, sub_bytes, hipMemcpyDeviceToHost, L.s));
+    if (out->err32)
+        HIP_TRY(hipMemcpyAsync(out->err32, d_e32, e32_bytes, hipMemcpyDeviceToHost, L.s));
+    if (out->plane)
+        HIP_TRY(hipMemcpy2DAsync(out->plane, out->plane_stride, po->pyr.lv[0].base, (size_t)po->pyr.lv[0].stride,
+                                 src_width, src_height, hipMemcpyDeviceToHost, L.s));
     HIP_TRY(hipStreamSynchronize(L.s));
     return SVTME_OK;
 }

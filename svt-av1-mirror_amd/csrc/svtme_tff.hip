@@ -6,7 +6,7 @@
 // accumulation over the window and the normalisation. Luma, 8-bit,
 // use_zz_based_filter == 0 only.
 //
-// Two kernels.
+// Three kernels.
 //
 // k_tff_pred, one 256-thread workgroup per (reference, SB), the whole window in
 // one launch. Wavefront 0 turns the SB's branch and split flags into a list of
@@ -25,6 +25,10 @@
 // k_tff_norm, one workgroup per SB: 1000 x centre plus the weighted tiles of
 // the references, normalised, 16 pixels per thread, into a dense device plane
 // of whole SBs, which the host copies out row by row.
+//
+// k_tff_norm_pic (svtme_tf_window), the same normalisation straight into the
+// padded level 0 of a resident picture, inside the aligned picture only; the
+// destination may be the centre picture's own plane.
 //
 // Semantics restated (reference line beside each):
 //  * tf_64x64_inter_prediction (temporal_filtering.c:2255-2361): one 64x64 block
@@ -80,6 +84,7 @@ struct TffArgs {
     uint32_t *wgt;                      // [n][sbs][16] weights, 32x32 block * 4 + quarter
     uint32_t *e32;                      // [n][sbs][4] 32x32 errors
     uint8_t *plane;                     // k_tff_norm: the filtered plane, whole SBs, stride pic_w_b64 * 64
+    DevPlane dst;                       // k_tff_norm_pic: level 0 of the result picture (may be cen)
     uint32_t decay, dist_th, ss;        // svtme_tf_filter_controls
     uint32_t n, sbs, pic_w_b64;
     int32_t W, H; // the 8-aligned picture
@@ -353,11 +358,11 @@ __global__ void __launch_bounds__(256) k_tff_pred(const TffArgs A) {
     }
 }
 
-__global__ void __launch_bounds__(256) k_tff_norm(const TffArgs A) {
-    const int tid      = threadIdx.x;
-    const uint32_t b64 = blockIdx.x;
-    const uint32_t sby = b64 / A.pic_w_b64, sbx = b64 - sby * A.pic_w_b64;
-    const int row = tid >> 2, c16 = tid & 3; // 16 pixels of one row, all in one 16x16 quarter
+// The normalisation of 16 pixels of one row of SB b64: row tid / 4, columns 16 (tid % 4) .. + 15 (all in
+// one 16x16 quarter), packed into four dwords. The only centre samples read are those 16.
+__device__ __forceinline__ void tff_norm16(const TffArgs &A, uint32_t b64, uint32_t sbx, uint32_t sby, int tid,
+                                           uint32_t o[4]) {
+    const int row = tid >> 2, c16 = tid & 3;
     const int wi = ((row >> 5) * 2 + (c16 >> 1)) * 4 + ((row >> 4) & 1) * 2 + (c16 & 1);
     const uint4 cv = *(const uint4 *)(A.cen.base + (ptrdiff_t)((int)sby * 64 + row) * A.cen.stride + (int)sbx * 64 + c16 * 16);
     const uint32_t cw[4] = {cv.x, cv.y, cv.z, cv.w};
@@ -376,7 +381,7 @@ __global__ void __launch_bounds__(256) k_tff_norm(const TffArgs A) {
     // (accum + (count >> 1)) / count (:2621): count <= 17000 and accum < 2^23, so the high product
     // by 2^32 / count rounded up is the quotient or one more
     const uint32_t m = 0xFFFFFFFFu / cnt + 1u;
-    uint32_t o[4] = {0, 0, 0, 0};
+    o[0] = o[1] = o[2] = o[3] = 0;
 #pragma unroll
     for (int k = 0; k < 16; k++) {
         const uint32_t v = acc[k] + (cnt >> 1);
@@ -384,25 +389,54 @@ __global__ void __launch_bounds__(256) k_tff_norm(const TffArgs A) {
         q -= q * cnt > v;
         o[k >> 2] |= q << (8 * (k & 3));
     }
+}
+
+__global__ void __launch_bounds__(256) k_tff_norm(const TffArgs A) {
+    const int tid      = threadIdx.x;
+    const uint32_t b64 = blockIdx.x;
+    const uint32_t sby = b64 / A.pic_w_b64, sbx = b64 - sby * A.pic_w_b64;
+    const int row = tid >> 2, c16 = tid & 3;
+    uint32_t o[4];
+    tff_norm16(A, b64, sbx, sby, tid, o);
     uint8_t *op = A.plane + ((size_t)sby * 64 + row) * ((size_t)A.pic_w_b64 * 64) + (size_t)sbx * 64 + c16 * 16;
     *(uint4 *)op = make_uint4(o[0], o[1], o[2], o[3]);
 }
 
+// The same into level 0 of a resident picture: only samples x < W, y < H of the aligned picture are
+// stored (W is a multiple of 8: a thread's 16 pixels are all inside, the first 8 inside, or all
+// outside), the margins are the pyramid kernels' to write afterwards. A.dst may be A.cen (the centre
+// picture replaced in place): a thread reads from the centre plane its own 16 pixels alone
+// (tff_norm16), before it stores them, and the samples nobody stores (x >= W or y >= H) are nobody's
+// input either, so no thread reads what another writes. k_tff_pred, which reads the centre widely,
+// has finished by stream order.
+__global__ void __launch_bounds__(256) k_tff_norm_pic(const TffArgs A) {
+    const int tid      = threadIdx.x;
+    const uint32_t b64 = blockIdx.x;
+    const uint32_t sby = b64 / A.pic_w_b64, sbx = b64 - sby * A.pic_w_b64;
+    const int x = (int)sbx * 64 + (tid & 3) * 16, y = (int)sby * 64 + (tid >> 2);
+    if (x >= A.W || y >= A.H)
+        return;
+    uint32_t o[4];
+    tff_norm16(A, b64, sbx, sby, tid, o);
+    uint8_t *op = A.dst.base + (ptrdiff_t)y * A.dst.stride + x; // 16-byte aligned, as the centre's load
+    if (x + 16 <= A.W)
+        *(uint4 *)op = make_uint4(o[0], o[1], o[2], o[3]);
+    else
+        *(uint2 *)op = make_uint2(o[0], o[1]);
+}
+
 // n references of one window: the predictions and weights in one launch, then the normalisation
-extern "C" hipError_t svtme_launch_tff(const DevPlane *cen, const DevPlane *ref, uint32_t n, uint32_t width,
-                                       uint32_t height, const svtme_tf_filter_controls *ctl,
-                                       const svtme_tf_subpel_sb *d_sub, uint8_t *d_tile, uint32_t *d_wgt,
-                                       uint32_t *d_e32, uint8_t *d_plane, hipStream_t s) {
+static hipError_t tff_args(TffArgs &A, const DevPlane *cen, const DevPlane *ref, uint32_t n, uint32_t width,
+                           uint32_t height, const svtme_tf_filter_controls *ctl, const svtme_tf_subpel_sb *d_sub,
+                           uint8_t *d_tile, uint32_t *d_wgt, uint32_t *d_e32) {
     if (!n || n > SVTME_MAX_BATCH_JOBS)
         return hipErrorInvalidValue;
-    TffArgs A{};
     A.cen = *cen;
     for (uint32_t k = 0; k < SVTME_MAX_BATCH_JOBS; k++) A.ref[k] = ref[k < n ? k : 0];
     A.sub       = d_sub;
     A.tile      = d_tile;
     A.wgt       = d_wgt;
     A.e32       = d_e32;
-    A.plane     = d_plane;
     A.decay     = ctl->tf_decay_factor_fp16;
     A.dist_th   = ctl->tf_mv_dist_th;
     A.ss        = ctl->sub_sampling_shift;
@@ -411,13 +445,45 @@ extern "C" hipError_t svtme_launch_tff(const DevPlane *cen, const DevPlane *ref,
     A.sbs       = A.pic_w_b64 * ((height + 63) / 64);
     A.W         = (int32_t)width;
     A.H         = (int32_t)height;
+    return hipSuccess;
+}
+
+extern "C" hipError_t svtme_launch_tff(const DevPlane *cen, const DevPlane *ref, uint32_t n, uint32_t width,
+                                       uint32_t height, const svtme_tf_filter_controls *ctl,
+                                       const svtme_tf_subpel_sb *d_sub, uint8_t *d_tile, uint32_t *d_wgt,
+                                       uint32_t *d_e32, uint8_t *d_plane, hipStream_t s) {
+    TffArgs A{};
+    const hipError_t e = tff_args(A, cen, ref, n, width, height, ctl, d_sub, d_tile, d_wgt, d_e32);
+    if (e != hipSuccess)
+        return e;
+    A.plane = d_plane;
     hipLaunchKernelGGL(k_tff_pred, dim3(n * A.sbs), dim3(256), 0, s, A);
     hipLaunchKernelGGL(k_tff_norm, dim3(A.sbs), dim3(256), 0, s, A);
+    return hipGetLastError();
+}
+
+// svtme_tf_window: the same two steps, the normalisation into level 0 of the result picture
+// (width x height, the window's aligned size; it may be the centre picture's own plane)
+extern "C" hipError_t svtme_launch_tff_pic(const DevPlane *cen, const DevPlane *ref, uint32_t n, uint32_t width,
+                                           uint32_t height, const svtme_tf_filter_controls *ctl,
+                                           const svtme_tf_subpel_sb *d_sub, uint8_t *d_tile, uint32_t *d_wgt,
+                                           uint32_t *d_e32, const DevPlane *dst, hipStream_t s) {
+    TffArgs A{};
+    const hipError_t e = tff_args(A, cen, ref, n, width, height, ctl, d_sub, d_tile, d_wgt, d_e32);
+    if (e != hipSuccess)
+        return e;
+    if (dst->width != (int32_t)width || dst->height != (int32_t)height)
+        return hipErrorInvalidValue;
+    A.dst = *dst;
+    hipLaunchKernelGGL(k_tff_pred, dim3(n * A.sbs), dim3(256), 0, s, A);
+    hipLaunchKernelGGL(k_tff_norm_pic, dim3(A.sbs), dim3(256), 0, s, A);
     return hipGetLastError();
 }
 
 extern "C" hipError_t svtme_prime_tff(void) { // (see svtme_prime_pyramid)
     hipFuncAttributes a;
     hipError_t e = hipFuncGetAttributes(&a, (const void *)k_tff_pred);
-    return e != hipSuccess ? e : hipFuncGetAttributes(&a, (const void *)k_tff_norm);
+    if (e == hipSuccess)
+        e = hipFuncGetAttributes(&a, (const void *)k_tff_norm);
+    return e != hipSuccess ? e : hipFuncGetAttributes(&a, (const void *)k_tff_norm_pic);
 }

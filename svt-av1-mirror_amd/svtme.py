@@ -276,6 +276,12 @@ class TfFilterControls(C.Structure):
         return {name: int(getattr(self, name)) for name, _ in self._fields_ if name != "pad"}
 
 
+class TfWindowOut(C.Structure):
+    """svtme_tf_window_out: host copies of a window's results, each pointer NULL or a buffer."""
+    _fields_ = [("plane", C.c_void_p), ("plane_stride", C.c_uint32), ("pad", C.c_uint32), ("records", C.c_void_p),
+                ("subpel", C.c_void_p), ("err32", C.c_void_p)]
+
+
 TAIL_BYTES = 24  # svtme_record_tail: the last 24 bytes of svtme_ref_record
 
 
@@ -726,6 +732,10 @@ def _job_api_protos(lib):
         _proto(lib, "svtme_tf_filter", "argtypes", [vp, C.c_uint64, C.POINTER(C.c_uint64), C.c_uint32, C.c_uint32,
                                                     C.c_uint32, C.POINTER(TfFilterControls), vp, vp, C.c_uint32, vp])
         _proto(lib, "svtme_tf_filter", "restype", C.c_int32)
+        _proto(lib, "svtme_tf_window", "argtypes", [vp, C.POINTER(Job), C.c_uint32, C.c_uint32, C.c_uint32,
+                                                    C.POINTER(TfSubpelControls), C.POINTER(TfFilterControls),
+                                                    C.c_uint64, C.POINTER(TfWindowOut)])
+        _proto(lib, "svtme_tf_window", "restype", C.c_int32)
         lib._svtme_protos = True
     return lib
 
@@ -1004,6 +1014,34 @@ class GpuME:
                                              subpel.ctypes.data, buf.ctypes.data, stride,
                                              err32.ctypes.data if with_err32 else None), "svtme_tf_filter")
         return buf[:, :width], err32
+
+    def tf_window(self, jobs, src_w: int, src_h: int, subpel_controls: TfSubpelControls,
+                  filter_controls: TfFilterControls, out_pn: int, want=("plane", "records", "subpel", "err32")):
+        """svtme_tf_window: the TF-ME jobs `jobs` of one window (one per reference, whole pictures),
+        the sub-pel refinement and the filter chained on the device; the filtered picture becomes the
+        resident picture `out_pn` (the centre's own number: in place). -> {name: array} of the
+        outputs named in `want`: plane [src_h, src_w] u8, records [n, SBs], subpel [n, SBs],
+        err32 [n, SBs, 4]. With nothing wanted the call returns once the work is queued."""
+        unknown = set(want) - {"plane", "records", "subpel", "err32"}
+        if unknown:
+            raise ValueError(f"unknown outputs {sorted(unknown)}")
+        n = len(jobs)
+        arr = (Job * max(n, 1))(*jobs)
+        sbs = sb_total(align8(src_w), align8(src_h))
+        res = {}
+        if "plane" in want:
+            res["plane"] = np.zeros((src_h, src_w), np.uint8)
+        if "records" in want:
+            res["records"] = np.zeros((n, sbs), REF_RECORD_DTYPE)
+        if "subpel" in want:
+            res["subpel"] = np.zeros((n, sbs), TF_SUBPEL_SB_DTYPE)
+        if "err32" in want:
+            res["err32"] = np.zeros((n, sbs, 4), np.uint32)
+        out = TfWindowOut(plane_stride=src_w, **{k: v.ctypes.data for k, v in res.items()})
+        self._check(self.lib.svtme_tf_window(self.ctx, arr, n, src_w, src_h, C.byref(subpel_controls),
+                                             C.byref(filter_controls), int(out_pn), C.byref(out) if res else None),
+                    "svtme_tf_window")
+        return res
 
     def device_records(self):
         n = C.c_uint64()
