@@ -84,7 +84,9 @@ typedef struct svtme_controls {
     /* number of HME-L0 search regions; only 2x2 is supported (motion_estimation.c:1875) */
     uint8_t num_hme_sa_w;
     uint8_t num_hme_sa_h;
-    /* search areas (MeHmeSearchAreaCtrls, me_context.h:342-347 / 421-429) */
+    /* search areas (MeHmeSearchAreaCtrls, me_context.h:342-347 / 421-429); a job is refused when
+     * hme_l2_sa.width exceeds 8192 with HME level 2 on, or when the widest full-pel area (me_sa max x
+     * the mv multiplier x 3/2 variance growth) exceeds 1016 positions with enable_me_sr_adjustment 2 */
     svtme_area_minmax hme_l0_sa;
     svtme_area hme_l1_sa;
     svtme_area hme_l2_sa;
@@ -98,7 +100,8 @@ typedef struct svtme_controls {
     uint32_t zz_sad_th;
     uint32_t phme_sad_th;
     uint16_t phme_sad_pct;
-    /* MeSrCtrls (me_context.h:292-305) */
+    /* MeSrCtrls (me_context.h:292-305); with enable_me_sr_adjustment and HME on, an open-loop job
+     * whose stationary_me_sr_divisor or me_sr_divisor_for_low_hme_sad is 0 is refused */
     uint8_t enable_me_sr_adjustment;
     uint8_t distance_based_hme_resizing;
     uint16_t reduce_me_sr_based_on_mv_length_th;

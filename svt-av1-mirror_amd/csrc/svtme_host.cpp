@@ -63,6 +63,7 @@ extern "C" void svtme_stage_a_list(const svtme_job *job, uint8_t *list, uint32_t
 extern "C" void svtme_stage_b_list(const svtme_job *job, uint8_t *list, uint32_t *count);
 extern "C" void svtme_stage_a1_list(const svtme_job *job, uint8_t *list, uint32_t *count);
 extern "C" uint32_t svtme_fp_parts_paths(const svtme_controls *c, uint32_t paths);
+extern "C" void svtme_fp_area_bound(const svtme_controls *c, uint32_t *w, uint32_t *h);
 extern "C" void svtme_hme_prepare(DevJob *dj);
 extern "C" bool svtme_hme_fused(const svtme_job *job);
 extern "C" bool svtme_hme_rt(const svtme_controls *c);
@@ -957,6 +958,24 @@ static svtme_status validate_job(svtme_ctx *c, const svtme_job *job, DevJob *dj,
                     job->me_type);
     if (job->width > 16384 || job->height > 16384)
         return fail(SVTME_ERR_BAD_PARAMETER, "picture too large for int16 search arithmetic");
+    // narrow fields of the kernels (svtme_stages.hip): the 13-bit column of k_hme's HME-L2 tile keys
+    // (hme_tile64), the 8-bit quad count of k_stage_c's full-pel windows (FpRef::nq, the per-SB kernel
+    // of enable_me_sr_adjustment == 2); and the divisors hme_prune_ref_and_adjust_sr divides by
+    const svtme_controls &ctl = job->ctrl;
+    if (ctl.enable_hme_flag && ctl.enable_hme_level2_flag && ctl.hme_l2_sa.width > 8192)
+        return fail(SVTME_ERR_BAD_PARAMETER, "hme_l2_sa.width %u exceeds the limit of 8192 positions",
+                    ctl.hme_l2_sa.width);
+    if (ctl.enable_me_sr_adjustment == 2) {
+        uint32_t bw, bh;
+        svtme_fp_area_bound(&ctl, &bw, &bh);
+        if (bw > 1016)
+            return fail(SVTME_ERR_BAD_PARAMETER, "full-pel search areas up to %u positions wide exceed the limit of "
+                                                 "1016 with enable_me_sr_adjustment 2", bw);
+    }
+    if (ctl.enable_me_sr_adjustment && ctl.enable_hme_flag && job->me_type != SVTME_ME_MCTF &&
+        (ctl.stationary_me_sr_divisor == 0 || ctl.me_sr_divisor_for_low_hme_sad == 0))
+        return fail(SVTME_ERR_BAD_PARAMETER, "stationary_me_sr_divisor and me_sr_divisor_for_low_hme_sad must be "
+                                             "non-zero with enable_me_sr_adjustment (a search-range divisor of 0)");
     const uint32_t total = svtme_sb_total(job->width, job->height);
     const uint32_t n     = job->sb_count ? job->sb_count : total - job->sb_begin;
     if (job->sb_begin >= total || job->sb_begin + n > total)

@@ -4823,6 +4823,8 @@ static void fp_area_bound(const svtme_controls *c, uint32_t *w, uint32_t *h) {
     *w = mw;
     *h = mh;
 }
+// the same bound for job validation (svtme_host.cpp)
+extern "C" void svtme_fp_area_bound(const svtme_controls *c, uint32_t *w, uint32_t *h) { fp_area_bound(c, w, h); }
 
 // Per-slot search parameters of k_hme that do not depend on the SB: the
 // distance, get_hme_l0_search_area (motion_estimation.c:1800-1867, here with

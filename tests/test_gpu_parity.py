@@ -687,7 +687,9 @@ def test_job_validation_errors(svtme, gpu):
     before anything is launched, and the context stays usable: a picture that is
     not resident, a size that is not a multiple of 8 or does not match the
     resident planes, an SB range outside the picture, reference counts beyond
-    the reference's 2 x 4, an unknown me_type."""
+    the reference's 2 x 4, an unknown me_type, an HME-L2 area wider than k_hme's tile
+    keys hold, a full-pel area wider than the per-SB kernel's windows hold, a zero
+    search-range divisor."""
     import copy
 
     S = svtme
@@ -715,6 +717,23 @@ def test_job_validation_errors(svtme, gpu):
     bad(lambda j: setattr(j, "sb_count", S.sb_total(w, h) + 1), "outside the picture")
     bad(lambda j: j.num_refs.__setitem__(0, 5), "reference counts")
     bad(lambda j: setattr(j, "me_type", 7), "me_type")
+
+    # the kernels' narrow fields and the search-range divisors (tests/me_sweep.py stays inside them)
+    def l2_too_wide(j):
+        j.ctrl.enable_hme_level2_flag = 1
+        j.ctrl.hme_l2_sa.width = 8200
+
+    def fullpel_too_wide(j):
+        j.ctrl.enable_me_sr_adjustment = 2
+        j.ctrl.me_sa.sa_min.width = j.ctrl.me_sa.sa_max.width = 1024
+
+    def zero_divisor(j):
+        j.ctrl.enable_me_sr_adjustment = 1
+        j.ctrl.me_sr_divisor_for_low_hme_sad = 0
+
+    bad(l2_too_wide, "limit of 8192")
+    bad(fullpel_too_wide, "limit of 1016")
+    bad(zero_divisor, "divisor of 0")
     # the context still serves a good job with the same result
     again, _ = gpu.submit(good)
     assert again.tobytes() == ok_recs.tobytes()
