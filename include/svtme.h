@@ -336,6 +336,42 @@ svtme_status svtme_picture_invalidate(svtme_ctx *ctx, uint64_t picture_number, c
 svtme_status svtme_picture_download(svtme_ctx *ctx, uint64_t picture_number, int level, uint8_t *dst,
                                     uint32_t *stride, uint32_t *width, uint32_t *height, uint32_t *pad);
 
+/* Resident chroma (8-bit, 4:2:0), for the chroma stage of temporal filtering
+ * (svtme_tf_filter_yuv, svtme_tf_window_yuv). Attach the Cb and Cr planes of a
+ * picture that is already resident: width x height is the LUMA source size the
+ * picture was uploaded with, the planes hold (width + 1) >> 1 x (height + 1) >> 1
+ * samples, rows `stride` bytes apart. They are padded by replication to W/2 x H/2
+ * of the 8-aligned picture (svt_aom_pad_picture_to_multiple_of_min_blk_size_dimensions
+ * on buffer_cb / buffer_cr, pic_analysis_process.c:1695-1711), then the margins
+ * are replicated (svt_aom_generate_padding, temporal_filtering.c:3916-3927) to a
+ * logical padding of SVTME_PAD_CHROMA.
+ *
+ * The padding is 40 where the reference's own is org_x >> 1 = 36: the chroma
+ * predictor of temporal filtering reaches 39 samples beyond an edge
+ * (clamp_mv_to_umv_border_sb with ss 1 and bw 32 lets a block start at -(4 + 32)
+ * with a non-zero phase, and the 8 taps read 3 further). For an MV that points 36
+ * or more chroma samples beyond an edge with a fractional phase the reference
+ * reads up to 3 bytes of the neighbouring row; this library defines those reads
+ * as replicated edge samples. TF-ME's search areas keep real MVs far from this.
+ *
+ * Synchronous, under the context lock; ordered after every job queued earlier on
+ * any lane that reads the picture and before every later one. The chroma is
+ * released with the picture; any later luma upload, svtme_picture_invalidate or
+ * svtme_tf_window result under the same number drops it (a stale plane is never
+ * silently kept). The luma calls never read it. Returns
+ * SVTME_ERR_BAD_PARAMETER before any GPU work for a NULL ctx / cb / cr, a zero
+ * size, a stride under the chroma width, a picture that is not resident or
+ * whose aligned size is not that of width x height. */
+#define SVTME_PAD_CHROMA 40
+svtme_status svtme_picture_upload_chroma(svtme_ctx *ctx, uint64_t picture_number, const uint8_t *cb,
+                                         const uint8_t *cr, uint32_t stride, uint32_t width, uint32_t height);
+/* Copy a resident chroma plane (1 = Cb, 2 = Cr) back to host, padding included, in
+ * the shape of svtme_picture_download: width x height are W/2 x H/2 of the aligned
+ * picture, pad is SVTME_PAD_CHROMA, dst (NULL: sizes only) gets (height + 2 pad)
+ * rows of stride = width + 2 pad bytes. Fails for a picture without chroma. */
+svtme_status svtme_picture_download_chroma(svtme_ctx *ctx, uint64_t picture_number, int plane, uint8_t *dst,
+                                           uint32_t *stride, uint32_t *width, uint32_t *height, uint32_t *pad);
+
 /* Run ME for one picture. `ref_records` receives sb_count x R records and
  * `sb_results` (may be NULL) sb_count results, in host memory. Synchronous. */
 svtme_status svtme_submit_picture(svtme_ctx *ctx, const svtme_job *job, svtme_ref_record *ref_records,
@@ -675,6 +711,80 @@ svtme_status svtme_tf_window(svtme_ctx *ctx, const svtme_job *jobs, uint32_t n, 
                              uint32_t src_height, const svtme_tf_subpel_controls *subpel_controls,
                              const svtme_tf_filter_controls *filter_controls, uint64_t out_picture_number,
                              const svtme_tf_window_out *out);
+
+/* ---------------------------------------------------------------------------
+ * Temporal filtering with chroma (tf_chroma set: TF levels 1..5, presets M0..M7;
+ * enc_handle.c tf_controls). 8-bit, 4:2:0, use_zz_based_filter == 0. Every
+ * picture of the window carries resident chroma (svtme_picture_upload_chroma).
+ * The chroma stage predicts, for every luma block of size b at (px, py) with MV
+ * mv, a b/2 x b/2 block of Cb and of Cr at (px / 2, py / 2) at the same MV read
+ * as 1/16 chroma pel (svt_aom_inter_prediction's chroma part,
+ * enc_inter_prediction.c:4248-4360; the 4x4 blocks with the 4-tap
+ * sub_pel_filters_4), and weights them per 8x8 quarter of each 16x16 chroma
+ * block (svt_av1_apply_temporal_filter_planewise_medium_partial_c, is_chroma 1:
+ * the luma MVs and block errors, (5 x chroma window error + luma window error) /
+ * 6, the plane's own decay factor). Reads beyond a chroma plane see replicated
+ * edge samples (see svtme_picture_upload_chroma: a deviation from the reference
+ * for MVs 36 or more chroma samples beyond an edge).
+ * ------------------------------------------------------------------------- */
+typedef struct svtme_tf_filter_yuv_controls {
+    svtme_tf_filter_controls luma;    /* as svtme_tf_filter takes them */
+    uint32_t tf_decay_factor_cb_fp16; /* MeContext.tf_decay_factor_fp16[C_U], any value */
+    uint32_t tf_decay_factor_cr_fp16; /* MeContext.tf_decay_factor_fp16[C_V], any value */
+} svtme_tf_filter_yuv_controls;       /* 16 bytes */
+
+typedef struct svtme_tf_filter_yuv_out {
+    uint8_t *y;         /* filtered luma, x < width, y < height (required) */
+    uint8_t *cb;        /* filtered Cb, x < (width + 1) >> 1, y < (height + 1) >> 1; may be NULL */
+    uint8_t *cr;        /* filtered Cr, likewise; may be NULL */
+    uint32_t y_stride;  /* bytes between rows, >= width; bytes beyond the plane's width are not written */
+    uint32_t cb_stride; /* >= (width + 1) >> 1 when cb is set */
+    uint32_t cr_stride; /* >= (width + 1) >> 1 when cr is set */
+    uint32_t pad;
+    uint32_t *err32;    /* NULL or n x SBs x 4, as svtme_tf_filter's err32_out */
+} svtme_tf_filter_yuv_out; /* 48 bytes */
+
+/* Host copies of a window's filtered chroma; every pointer may be NULL. */
+typedef struct svtme_tf_window_yuv_out {
+    uint8_t *cb;        /* x < (src_width + 1) >> 1, y < (src_height + 1) >> 1 */
+    uint8_t *cr;
+    uint32_t cb_stride; /* >= (src_width + 1) >> 1 when cb is set */
+    uint32_t cr_stride;
+} svtme_tf_window_yuv_out; /* 24 bytes */
+#ifdef __cplusplus
+static_assert(sizeof(svtme_tf_filter_yuv_controls) == 16 && sizeof(svtme_tf_filter_yuv_out) == 48 &&
+                  sizeof(svtme_tf_window_yuv_out) == 24, "svtme_tf_*_yuv layout");
+#else
+_Static_assert(sizeof(svtme_tf_filter_yuv_controls) == 16 && sizeof(svtme_tf_filter_yuv_out) == 48 &&
+                   sizeof(svtme_tf_window_yuv_out) == 24, "svtme_tf_*_yuv layout");
+#endif
+
+/* svtme_tf_filter with the chroma stage: the same arguments, the controls with
+ * the two chroma decay factors and the outputs in a struct. out->y and
+ * out->err32 receive byte for byte what svtme_tf_filter writes; out->cb and
+ * out->cr what svt_aom_get_final_filtered_pixels_c leaves in the centre
+ * picture's chroma. No resident picture is modified. Synchronous. Errors: those
+ * of svtme_tf_filter (out, out->y in the place of its out), and before any GPU
+ * work too a chroma stride under the chroma width and a picture of the window
+ * without chroma. */
+svtme_status svtme_tf_filter_yuv(svtme_ctx *ctx, uint64_t centre_picture_number, const uint64_t *ref_picture_numbers,
+                                 uint32_t n, uint32_t width, uint32_t height,
+                                 const svtme_tf_filter_yuv_controls *controls, const svtme_tf_subpel_sb *subpel,
+                                 const svtme_tf_filter_yuv_out *out);
+
+/* svtme_tf_window with the chroma stage chained on lane 0's stream after the luma
+ * prediction. The result picture also gets chroma planes: the filtered samples
+ * inside the true chroma size, re-padded beyond it with the margins, as
+ * svtme_picture_upload_chroma of the filtered planes would leave them. In place
+ * (out_picture_number the centre's) the centre's chroma is replaced too. `out` is
+ * svtme_tf_window's, `out_uv` (NULL or every pointer NULL: nothing copied) asks
+ * for the chroma host copies. The luma side, the ordering guarantees and the
+ * refusals are svtme_tf_window's; refused too, before any GPU work, are a chroma
+ * stride under the chroma width and a picture of the window without chroma. */
+svtme_status svtme_tf_window_yuv(svtme_ctx *ctx, const svtme_job *jobs, uint32_t n, uint32_t src_width,
+                                 uint32_t src_height, const svtme_tf_subpel_controls *subpel_controls,
+                                 const svtme_tf_filter_yuv_controls *filter_controls, uint64_t out_picture_number,
+                                 const svtme_tf_window_out *out, const svtme_tf_window_yuv_out *out_uv);
 
 /* Number of 64x64 SBs of a width x height picture, and R for a job. */
 uint32_t svtme_sb_total(uint32_t width, uint32_t height);

@@ -25,6 +25,14 @@ struct DevPlane {
     int32_t pad;     // logical padding (org_x == org_y of the reference plane)
 };
 
+// Chroma planes (svtme_picture_upload_chroma; 8-bit 4:2:0). The LOGICAL padding is
+// SVTME_PAD_CHROMA (40): the chroma predictor of temporal filtering reaches 39
+// samples beyond each edge. The device margins are 48 on the left
+// and at least 48 on the right (16-byte aligned interior row starts, 8 bytes of
+// slack beyond the padding for aligned dword loads), 40 rows above and below.
+#define SVTME_DEV_C_LEFT 48
+#define SVTME_DEV_C_TOP 40
+
 struct DevPyramid {
     DevPlane lv[3];  // 0 = full, 1 = quarter, 2 = sixteenth
 };
@@ -127,3 +135,31 @@ static inline void svtme_plane_geometry(int level, uint32_t W, uint32_t H, uint3
     }
     *rows = *h + 2 * *top;
 }
+
+// chroma plane geometry (Cb and Cr alike) for an aligned W x H picture, 4:2:0
+static inline void svtme_chroma_geometry(uint32_t W, uint32_t H, uint32_t *w, uint32_t *h, uint32_t *left,
+                                         uint32_t *top, uint32_t *stride, uint32_t *rows) {
+    *w = W / 2, *h = H / 2, *left = SVTME_DEV_C_LEFT, *top = SVTME_DEV_C_TOP;
+    *stride = svtme_round_up(W / 2 + SVTME_DEV_C_LEFT + 48, 64);
+    *rows   = *h + 2 * *top;
+}
+
+// Arguments of the chroma stage of temporal filtering (svtme_tff.hip: k_tff_pred_uv, k_tff_norm_uv,
+// k_tff_norm_uv_pic), filled by the host. Plane 0 is Cb, 1 is Cr; every picture of a window has the
+// same chroma geometry, so the references are base pointers with one stride.
+struct TffcArgs {
+    DevPlane cen_y;                                // level 0 of the centre picture
+    DevPlane cen[2];                               // its chroma planes
+    const uint8_t *ref[2][SVTME_MAX_BATCH_JOBS];   // interior sample (0, 0) of the references' chroma planes
+    int32_t ref_stride;
+    const svtme_tf_subpel_sb *sub;                 // [n][sbs]
+    const uint8_t *tile_y;                         // [n][sbs][64 * 64] luma predictions (k_tff_pred)
+    const uint32_t *e32;                           // [n][sbs][4] 32x32 errors (k_tff_pred)
+    uint8_t *tile;                                 // [n][sbs][2][32 * 32] chroma predictions
+    uint32_t *wgt;                                 // [n][sbs][2][16] chroma weights
+    uint8_t *plane;                                // k_tff_norm_uv: [2] planes of whole SBs, stride pic_w_b64 * 32
+    DevPlane dst[2];                               // k_tff_norm_uv_pic: the result picture's chroma (may be cen)
+    uint32_t decay_cb, decay_cr, dist_th;
+    uint32_t n, sbs, pic_w_b64;
+    int32_t W, H;                                  // the 8-aligned luma size
+};

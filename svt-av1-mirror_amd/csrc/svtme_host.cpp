@@ -55,6 +55,11 @@ extern "C" hipError_t svtme_launch_tff(const DevPlane *cen, const DevPlane *ref,
                                        uint32_t height, const svtme_tf_filter_controls *ctl,
                                        const svtme_tf_subpel_sb *d_sub, uint8_t *d_tile, uint32_t *d_wgt,
                                        uint32_t *d_e32, uint8_t *d_plane, hipStream_t s);
+extern "C" hipError_t svtme_launch_tffc(const TffcArgs *A, hipStream_t s);
+extern "C" hipError_t svtme_launch_tff_pic_yuv(const DevPlane *cen, const DevPlane *ref, uint32_t n, uint32_t width,
+                                               uint32_t height, const svtme_tf_filter_controls *ctl,
+                                               const svtme_tf_subpel_sb *d_sub, uint8_t *d_tile, uint32_t *d_wgt,
+                                               uint32_t *d_e32, const DevPlane *dst, const TffcArgs *U, hipStream_t s);
 extern "C" hipError_t svtme_launch_tff_pic(const DevPlane *cen, const DevPlane *ref, uint32_t n, uint32_t width,
                                            uint32_t height, const svtme_tf_filter_controls *ctl,
                                            const svtme_tf_subpel_sb *d_sub, uint8_t *d_tile, uint32_t *d_wgt,
@@ -108,7 +113,12 @@ struct PicBuf {
     size_t bytes = 0;
     uint32_t W = 0, H = 0;
     DevPyramid pyr{};
-    hipEvent_t ready = nullptr;           // end of an asynchronous upload on the upload stream
+    // attached chroma (svtme_picture_upload_chroma, svtme_tf_window_yuv): a buffer of its own, so the
+    // luma geometry and svtme_reserve_pictures know nothing of it; nullptr: the picture has none
+    uint8_t *cmem = nullptr;
+    size_t cbytes = 0;
+    DevPlane chroma[2]{}; // Cb, Cr
+    hipEvent_t ready = nullptr;          // end of an asynchronous upload on the upload stream
     uint32_t pending = 0;                 // lanes whose stream has not waited on `ready` yet
     hipEvent_t used[SVTME_LANES] = {};    // end of the last submission of each lane that reads the
                                           // picture (a lane's submission event, not owned)
@@ -183,6 +193,7 @@ struct svtme_ctx {
     void *d_tfsp    = nullptr; // svtme_tf_subpel: n x SBs records | n x SBs results
     size_t tfsp_cap = 0;
     void *d_tff     = nullptr; // svtme_tf_filter: results of the sub-pel stage | tiles | weights | errors | plane
+                               // (the yuv calls: | chroma tiles | chroma weights | chroma planes)
     size_t tff_cap  = 0;
     uint32_t last_count = 0, last_R = 0;
     bool last_has_sb    = false;
@@ -294,11 +305,15 @@ extern "C" void svtme_ctx_destroy(svtme_ctx *c) {
         (void)hipStreamSynchronize(c->ustream);
     for (auto &kv : c->pics) {
         (void)hipFree(kv.second.mem);
+        if (kv.second.cmem)
+            (void)hipFree(kv.second.cmem);
         if (kv.second.ready)
             (void)hipEventDestroy(kv.second.ready);
     }
     for (auto &g : c->graves) {
         (void)hipFree(g.mem);
+        if (g.cmem)
+            (void)hipFree(g.cmem);
         if (g.ready)
             (void)hipEventDestroy(g.ready);
     }
@@ -469,6 +484,12 @@ static uint8_t *sweep_graves(svtme_ctx *c, size_t want) {
             c->freebufs.emplace_back(g.bytes, g.mem);
         else
             (void)hipFree(g.mem);
+        if (g.cmem) { // the chroma attached to a released picture goes with it
+            if (c->freebufs.size() < svtme_ctx::kMaxFree)
+                c->freebufs.emplace_back(g.cbytes, g.cmem);
+            else
+                (void)hipFree(g.cmem);
+        }
         c->graves[i] = c->graves.back();
         c->graves.pop_back();
     }
@@ -513,9 +534,59 @@ static svtme_status pic_mem(svtme_ctx *c, size_t total, uint8_t **out) {
     return SVTME_OK;
 }
 
-// allocate the three planes of a W x H picture in one buffer
-static svtme_status alloc_pic(svtme_ctx *c, uint64_t pn, uint32_t W, uint32_t H, PicBuf **out) {
+// bytes of the two padded chroma planes of a W x H picture in one buffer, and the second's offset
+static size_t chroma_bytes(uint32_t W, uint32_t H, size_t *second = nullptr) {
+    uint32_t w, h, left, top, stride, rows;
+    svtme_chroma_geometry(W, H, &w, &h, &left, &top, &stride, &rows);
+    const size_t one = ((size_t)stride * rows + 255) & ~(size_t)255;
+    if (second)
+        *second = one;
+    return 2 * one + 256;
+}
+
+// The picture's luma is about to be replaced: its chroma no longer belongs to it. The buffer goes to
+// the graves with the picture's reader events (work queued earlier may still read it).
+static void drop_chroma(svtme_ctx *c, PicBuf &pb) {
+    if (!pb.cmem)
+        return;
+    PicBuf g;
+    g.mem = pb.cmem, g.bytes = pb.cbytes;
+    for (int l = 0; l < SVTME_LANES; l++) g.used[l] = pb.used[l];
+    c->graves.push_back(g);
+    pb.cmem = nullptr, pb.cbytes = 0;
+    pb.chroma[0] = pb.chroma[1] = DevPlane{};
+}
+
+// chroma planes for a resident picture that has none (contents undefined until written)
+static svtme_status alloc_chroma(svtme_ctx *c, PicBuf &pb) {
+    if (pb.cmem)
+        return SVTME_OK;
+    size_t second;
+    const size_t total = chroma_bytes(pb.W, pb.H, &second);
+    svtme_status st    = pic_mem(c, total, &pb.cmem);
+    if (st)
+        return st;
+    pb.cbytes = total;
+    uint32_t w, h, left, top, stride, rows;
+    svtme_chroma_geometry(pb.W, pb.H, &w, &h, &left, &top, &stride, &rows);
+    for (int p = 0; p < 2; p++) {
+        DevPlane &d = pb.chroma[p];
+        d.base      = pb.cmem + p * second + (size_t)top * stride + left;
+        d.stride    = (int32_t)stride;
+        d.width     = (int32_t)w;
+        d.height    = (int32_t)h;
+        d.pad       = SVTME_PAD_CHROMA;
+    }
+    return SVTME_OK;
+}
+
+// allocate the three planes of a W x H picture in one buffer; chroma attached to an earlier picture
+// of the number is dropped unless the caller writes it too (svtme_tf_window_yuv)
+static svtme_status alloc_pic(svtme_ctx *c, uint64_t pn, uint32_t W, uint32_t H, PicBuf **out,
+                              bool keep_chroma = false) {
     auto it = c->pics.find(pn);
+    if (it != c->pics.end() && it->second.W == W && it->second.H == H && !keep_chroma)
+        drop_chroma(c, it->second);
     if (it != c->pics.end() && (it->second.W != W || it->second.H != H)) {
         // a new size: the old buffer goes to the graves (freed for reuse once its readers ran)
         c->graves.push_back(it->second);
@@ -919,6 +990,83 @@ extern "C" svtme_status svtme_picture_download(svtme_ctx *c, uint64_t pn, int le
         return fail(SVTME_ERR_BAD_PARAMETER, "svtme_picture_download: picture %llu not resident",
                     (unsigned long long)pn);
     const DevPlane &p = it->second.pyr.lv[level];
+    const uint32_t S  = (uint32_t)(p.width + 2 * p.pad);
+    if (stride)
+        *stride = S;
+    if (width)
+        *width = (uint32_t)p.width;
+    if (height)
+        *height = (uint32_t)p.height;
+    if (pad)
+        *pad = (uint32_t)p.pad;
+    if (!dst)
+        return SVTME_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    svtme_status qs = quiesce(c);
+    if (qs)
+        return qs;
+    HIP_TRY(hipMemcpy2D(dst, S, p.base - (ptrdiff_t)p.pad * p.stride - p.pad, (size_t)p.stride, S,
+                        (size_t)(p.height + 2 * p.pad), hipMemcpyDeviceToHost));
+    return SVTME_OK;
+}
+
+// The padded chroma plane from cw x ch true samples (src may be the plane's own interior): the
+// replication to W/2 x H/2 and the margins are one clamp of the source coordinate, k_build_full's
+static svtme_status build_chroma(const PicBuf *pb, int plane, const void *dsrc, uint32_t src_stride, uint32_t cw,
+                                 uint32_t ch, hipStream_t st) {
+    uint32_t w, h, left, top, stride, rows;
+    svtme_chroma_geometry(pb->W, pb->H, &w, &h, &left, &top, &stride, &rows);
+    HIP_TRY(svtme_launch_build_full(dsrc, src_stride, (int)cw, (int)ch, 0, pb->chroma[plane], (int)left, (int)top,
+                                    (int)rows, st));
+    return SVTME_OK;
+}
+
+extern "C" svtme_status svtme_picture_upload_chroma(svtme_ctx *c, uint64_t pn, const uint8_t *cb, const uint8_t *cr,
+                                                    uint32_t stride, uint32_t w, uint32_t h) {
+    if (!c || !cb || !cr || w == 0 || h == 0)
+        return fail(SVTME_ERR_BAD_PARAMETER, "svtme_picture_upload_chroma: null ctx, cb or cr, or a %ux%u picture", w, h);
+    const uint32_t cw = (w + 1) >> 1, ch = (h + 1) >> 1;
+    if (stride < cw)
+        return fail(SVTME_ERR_BAD_PARAMETER, "svtme_picture_upload_chroma: stride %u under the chroma width %u", stride,
+                    cw);
+    std::lock_guard<std::mutex> lk(c->mu);
+    auto it = c->pics.find(pn);
+    if (it == c->pics.end())
+        return fail(SVTME_ERR_BAD_PARAMETER, "svtme_picture_upload_chroma: picture %llu is not resident",
+                    (unsigned long long)pn);
+    PicBuf &pb = it->second;
+    if (pb.W != svtme_align8_u(w) || pb.H != svtme_align8_u(h))
+        return fail(SVTME_ERR_BAD_PARAMETER, "svtme_picture_upload_chroma: picture %llu is %ux%u, the chroma's %ux%u",
+                    (unsigned long long)pn, pb.W, pb.H, w, h);
+    HIP_TRY(hipSetDevice(c->device));
+    svtme_status st;
+    const size_t one = (size_t)cw * ch;
+    if ((st = alloc_chroma(c, pb)) || (st = ensure_buf(&c->staging, &c->staging_cap, 2 * one)))
+        return st;
+    uint8_t *stg = (uint8_t *)c->staging; // (reused in stream order, as upload_host does)
+    HIP_TRY(hipMemcpy2DAsync(stg, cw, cb, stride, cw, ch, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpy2DAsync(stg + one, cw, cr, stride, cw, ch, hipMemcpyHostToDevice, c->stream));
+    // queued jobs of the other lanes may still read the old planes (lane 0's run before by stream order)
+    if ((st = after_readers(c, pb, c->stream)) || (st = build_chroma(&pb, 0, stg, cw, cw, ch, c->stream)) ||
+        (st = build_chroma(&pb, 1, stg + one, cw, cw, ch, c->stream)))
+        return st;
+    // later jobs of the other lanes wait for the planes: the stream is drained before the call returns
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return SVTME_OK;
+}
+
+// Copy one chroma plane back in the shape of svtme_picture_download: (h + 2 pad) rows of (w + 2 pad) bytes
+extern "C" svtme_status svtme_picture_download_chroma(svtme_ctx *c, uint64_t pn, int plane, uint8_t *dst,
+                                                      uint32_t *stride, uint32_t *width, uint32_t *height,
+                                                      uint32_t *pad) {
+    if (!c || plane < 1 || plane > 2)
+        return fail(SVTME_ERR_BAD_PARAMETER, "svtme_picture_download_chroma: null ctx or plane %d (1 = Cb, 2 = Cr)", plane);
+    std::lock_guard<std::mutex> lk(c->mu);
+    auto it = c->pics.find(pn);
+    if (it == c->pics.end() || !it->second.cmem)
+        return fail(SVTME_ERR_BAD_PARAMETER, "svtme_picture_download_chroma: picture %llu %s", (unsigned long long)pn,
+                    it == c->pics.end() ? "is not resident" : "has no chroma");
+    const DevPlane &p = it->second.chroma[plane - 1];
     const uint32_t S  = (uint32_t)(p.width + 2 * p.pad);
     if (stride)
         *stride = S;
@@ -1756,46 +1904,97 @@ extern "C" svtme_status svtme_tf_subpel(svtme_ctx *c, uint64_t centre_picture_nu
 // Temporal filtering's luma prediction and weighting (svtme_tff.hip). Held under
 // the context lock from the launch to the copy-out, as svtme_tf_subpel is.
 // ----------------------------------------------------------------------------
-extern "C" svtme_status svtme_tf_filter(svtme_ctx *c, uint64_t centre_picture_number,
-                                        const uint64_t *ref_picture_numbers, uint32_t n, uint32_t width,
-                                        uint32_t height, const svtme_tf_filter_controls *ctl,
-                                        const svtme_tf_subpel_sb *subpel, uint8_t *out, uint32_t out_stride,
-                                        uint32_t *err32_out) {
+// the chroma side of svtme_tf_filter_yuv / svtme_tf_window_yuv: the decay factors and the host copies
+struct TfChroma {
+    uint32_t decay[2];
+    uint8_t *out[2]; // Cb, Cr; either may be NULL
+    uint32_t stride[2];
+};
+
+// checked before any GPU work: a stride under the chroma width
+static svtme_status chroma_strides_ok(const char *fn, const TfChroma *uv, uint32_t width) {
+    for (int p = 0; p < 2; p++)
+        if (uv->out[p] && uv->stride[p] < (width + 1) >> 1)
+            return fail(SVTME_ERR_BAD_PARAMETER, "%s: %s stride %u under the chroma width %u", fn, p ? "cr" : "cb",
+                        uv->stride[p], (width + 1) >> 1);
+    return SVTME_OK;
+}
+
+// the chroma stage's arguments over the luma stage's scratch; the chroma sections follow `d_end`
+// (16-byte aligned): tiles | weights | (dense) the two planes
+static void tffc_fill(TffcArgs &A, PicBuf *const *pb, uint32_t n, uint32_t W, uint32_t H,
+                      const svtme_tf_filter_controls *ctl, const TfChroma *uv, const svtme_tf_subpel_sb *d_sub,
+                      const uint8_t *d_tile, const uint32_t *d_e32, uint8_t *d_end) {
+    const size_t units = (size_t)n * svtme_sb_total(W, H);
+    A.cen_y = pb[0]->pyr.lv[0];
+    for (int p = 0; p < 2; p++) {
+        A.cen[p] = pb[0]->chroma[p];
+        for (uint32_t k = 0; k < SVTME_MAX_BATCH_JOBS; k++) A.ref[p][k] = pb[k < n ? k + 1 : 1]->chroma[p].base;
+    }
+    A.ref_stride = pb[1]->chroma[0].stride;
+    A.sub        = d_sub;
+    A.tile_y     = d_tile;
+    A.e32        = d_e32;
+    A.tile       = d_end;
+    A.wgt        = (uint32_t *)(d_end + 2048 * units);
+    A.plane      = d_end + 2048 * units + 128 * units;
+    A.decay_cb   = uv->decay[0];
+    A.decay_cr   = uv->decay[1];
+    A.dist_th    = ctl->tf_mv_dist_th;
+    A.n          = n;
+    A.pic_w_b64  = (W + 63) / 64;
+    A.sbs        = svtme_sb_total(W, H);
+    A.W          = (int32_t)W;
+    A.H          = (int32_t)H;
+}
+
+// svtme_tf_filter (uv NULL) and svtme_tf_filter_yuv
+static svtme_status tf_filter_impl(const char *fn, const TfChroma *uv, svtme_ctx *c, uint64_t centre_picture_number,
+                                   const uint64_t *ref_picture_numbers, uint32_t n, uint32_t width, uint32_t height,
+                                   const svtme_tf_filter_controls *ctl, const svtme_tf_subpel_sb *subpel, uint8_t *out,
+                                   uint32_t out_stride, uint32_t *err32_out) {
     if (!c || !ref_picture_numbers || !ctl || !subpel || !out)
-        return fail(SVTME_ERR_BAD_PARAMETER, "svtme_tf_filter: null ctx, ref_picture_numbers, controls, subpel or out");
+        return fail(SVTME_ERR_BAD_PARAMETER, "%s: null ctx, ref_picture_numbers, controls, subpel or out", fn);
     if (n < 1 || n > SVTME_MAX_BATCH_JOBS)
-        return fail(SVTME_ERR_BAD_PARAMETER, "svtme_tf_filter: %u references (1..%d)", n, SVTME_MAX_BATCH_JOBS);
+        return fail(SVTME_ERR_BAD_PARAMETER, "%s: %u references (1..%d)", fn, n, SVTME_MAX_BATCH_JOBS);
     if (!tff_controls_ok(ctl))
         return fail(SVTME_ERR_BAD_PARAMETER,
-                    "svtme_tf_filter: controls out of range: tf_mv_dist_th %u (0..32767), sub_sampling_shift %u (0..1)",
+                    "%s: controls out of range: tf_mv_dist_th %u (0..32767), sub_sampling_shift %u (0..1)", fn,
                     ctl->tf_mv_dist_th, ctl->sub_sampling_shift);
     if (!width || !height)
-        return fail(SVTME_ERR_BAD_PARAMETER, "svtme_tf_filter: %ux%u picture", width, height);
+        return fail(SVTME_ERR_BAD_PARAMETER, "%s: %ux%u picture", fn, width, height);
     if (out_stride < width)
-        return fail(SVTME_ERR_BAD_PARAMETER, "svtme_tf_filter: out_stride %u under the width %u", out_stride, width);
+        return fail(SVTME_ERR_BAD_PARAMETER, "%s: out_stride %u under the width %u", fn, out_stride, width);
+    if (uv && chroma_strides_ok(fn, uv, width))
+        return SVTME_ERR_BAD_PARAMETER;
     const uint32_t W = svtme_align8_u(width), H = svtme_align8_u(height);
     const uint32_t sbs = svtme_sb_total(W, H);
     for (size_t k = 0; k < (size_t)n * sbs; k++)
         if (subpel[k].branch > SVTME_TFSP_32)
-            return fail(SVTME_ERR_BAD_PARAMETER, "svtme_tf_filter: subpel[%zu].branch is %u (0..2)", k, subpel[k].branch);
+            return fail(SVTME_ERR_BAD_PARAMETER, "%s: subpel[%zu].branch is %u (0..2)", fn, k, subpel[k].branch);
     std::lock_guard<std::mutex> lk(c->mu);
     PicBuf *pb[SVTME_MAX_BATCH_JOBS + 1];
     for (uint32_t k = 0; k <= n; k++) {
         const uint64_t pn = k ? ref_picture_numbers[k - 1] : centre_picture_number;
         auto it           = c->pics.find(pn);
         if (it == c->pics.end())
-            return fail(SVTME_ERR_BAD_PARAMETER, "svtme_tf_filter: picture %llu is not resident", (unsigned long long)pn);
+            return fail(SVTME_ERR_BAD_PARAMETER, "%s: picture %llu is not resident", fn, (unsigned long long)pn);
         pb[k] = &it->second;
         if (pb[k]->W != W || pb[k]->H != H)
-            return fail(SVTME_ERR_BAD_PARAMETER, "svtme_tf_filter: picture %llu is %ux%u, the window %ux%u",
+            return fail(SVTME_ERR_BAD_PARAMETER, "%s: picture %llu is %ux%u, the window %ux%u", fn,
                         (unsigned long long)pn, pb[k]->W, pb[k]->H, W, H);
+        if (uv && !pb[k]->cmem)
+            return fail(SVTME_ERR_BAD_PARAMETER, "%s: picture %llu has no chroma", fn, (unsigned long long)pn);
     }
     HIP_TRY(hipSetDevice(c->device));
-    // results of the sub-pel stage | tiles | weights | errors | the plane, whole SBs
+    // results of the sub-pel stage | tiles | weights | errors | the plane, whole SBs; with chroma then
+    // its tiles | weights | two planes, whole SBs
     const size_t units = (size_t)n * sbs, pstride = (size_t)((W + 63) / 64) * 64;
     const size_t sub_bytes = sizeof(svtme_tf_subpel_sb) * units, tile_bytes = 4096 * units, wgt_bytes = 64 * units,
                  e32_bytes = 16 * units, plane_bytes = 4096 * (size_t)sbs;
-    svtme_status st = ensure_buf(&c->d_tff, &c->tff_cap, sub_bytes + tile_bytes + wgt_bytes + e32_bytes + plane_bytes);
+    const size_t uv_bytes = uv ? (2048 + 128) * units + 2048 * (size_t)sbs : 0;
+    svtme_status st =
+        ensure_buf(&c->d_tff, &c->tff_cap, sub_bytes + tile_bytes + wgt_bytes + e32_bytes + plane_bytes + uv_bytes);
     if (st)
         return st;
     DevPlane ref[SVTME_MAX_BATCH_JOBS];
@@ -1814,6 +2013,11 @@ extern "C" svtme_status svtme_tf_filter(svtme_ctx *c, uint64_t centre_picture_nu
     uint8_t *d_plane          = d_tile + tile_bytes + wgt_bytes + e32_bytes;
     HIP_TRY(hipMemcpyAsync(d_sub, subpel, sub_bytes, hipMemcpyHostToDevice, L.s));
     HIP_TRY(svtme_launch_tff(&pb[0]->pyr.lv[0], ref, n, W, H, ctl, d_sub, d_tile, d_wgt, d_e32, d_plane, L.s));
+    TffcArgs U{};
+    if (uv) {
+        tffc_fill(U, pb, n, W, H, ctl, uv, d_sub, d_tile, d_e32, d_plane + plane_bytes);
+        HIP_TRY(svtme_launch_tffc(&U, L.s));
+    }
     hipEvent_t done = L.ev[L.ev_next];
     L.ev_next       = (L.ev_next + 1) % Lane::kEv;
     HIP_TRY(hipEventRecord(done, L.s));
@@ -1821,8 +2025,34 @@ extern "C" svtme_status svtme_tf_filter(svtme_ctx *c, uint64_t centre_picture_nu
     HIP_TRY(hipMemcpy2DAsync(out, out_stride, d_plane, pstride, width, height, hipMemcpyDeviceToHost, L.s));
     if (err32_out)
         HIP_TRY(hipMemcpyAsync(err32_out, d_e32, e32_bytes, hipMemcpyDeviceToHost, L.s));
+    for (int p = 0; uv && p < 2; p++)
+        if (uv->out[p])
+            HIP_TRY(hipMemcpy2DAsync(uv->out[p], uv->stride[p], U.plane + (size_t)p * 1024 * sbs, pstride / 2,
+                                     (width + 1) >> 1, (height + 1) >> 1, hipMemcpyDeviceToHost, L.s));
     HIP_TRY(hipStreamSynchronize(L.s));
     return SVTME_OK;
+}
+
+extern "C" svtme_status svtme_tf_filter(svtme_ctx *c, uint64_t centre_picture_number,
+                                        const uint64_t *ref_picture_numbers, uint32_t n, uint32_t width,
+                                        uint32_t height, const svtme_tf_filter_controls *ctl,
+                                        const svtme_tf_subpel_sb *subpel, uint8_t *out, uint32_t out_stride,
+                                        uint32_t *err32_out) {
+    return tf_filter_impl("svtme_tf_filter", nullptr, c, centre_picture_number, ref_picture_numbers, n, width, height,
+                          ctl, subpel, out, out_stride, err32_out);
+}
+
+extern "C" svtme_status svtme_tf_filter_yuv(svtme_ctx *c, uint64_t centre_picture_number,
+                                            const uint64_t *ref_picture_numbers, uint32_t n, uint32_t width,
+                                            uint32_t height, const svtme_tf_filter_yuv_controls *ctl,
+                                            const svtme_tf_subpel_sb *subpel, const svtme_tf_filter_yuv_out *out) {
+    if (!ctl || !out)
+        return fail(SVTME_ERR_BAD_PARAMETER, "svtme_tf_filter_yuv: null controls or out");
+    const TfChroma uv = {{ctl->tf_decay_factor_cb_fp16, ctl->tf_decay_factor_cr_fp16},
+                         {out->cb, out->cr},
+                         {out->cb_stride, out->cr_stride}};
+    return tf_filter_impl("svtme_tf_filter_yuv", &uv, c, centre_picture_number, ref_picture_numbers, n, width, height,
+                          &ctl->luma, subpel, out->y, out->y_stride, out->err32);
 }
 
 // ----------------------------------------------------------------------------
@@ -1831,75 +2061,82 @@ extern "C" svtme_status svtme_tf_filter(svtme_ctx *c, uint64_t centre_picture_nu
 // stream through the two stages' scratch. Held under the context lock from the
 // first launch to the last copy.
 // ----------------------------------------------------------------------------
-extern "C" svtme_status svtme_tf_window(svtme_ctx *c, const svtme_job *jobs, uint32_t n, uint32_t src_width,
-                                        uint32_t src_height, const svtme_tf_subpel_controls *sp_ctl,
-                                        const svtme_tf_filter_controls *f_ctl, uint64_t out_pn,
-                                        const svtme_tf_window_out *out) {
+// svtme_tf_window (uv NULL) and svtme_tf_window_yuv
+static svtme_status tf_window_impl(const char *fn, const TfChroma *uv, svtme_ctx *c, const svtme_job *jobs, uint32_t n,
+                                   uint32_t src_width, uint32_t src_height, const svtme_tf_subpel_controls *sp_ctl,
+                                   const svtme_tf_filter_controls *f_ctl, uint64_t out_pn,
+                                   const svtme_tf_window_out *out) {
     if (!c || !jobs || !sp_ctl || !f_ctl)
-        return fail(SVTME_ERR_BAD_PARAMETER, "svtme_tf_window: null ctx, jobs, subpel_controls or filter_controls");
+        return fail(SVTME_ERR_BAD_PARAMETER, "%s: null ctx, jobs, subpel_controls or filter_controls", fn);
     if (n < 1 || n > SVTME_MAX_BATCH_JOBS)
-        return fail(SVTME_ERR_BAD_PARAMETER, "svtme_tf_window: %u jobs (1..%d)", n, SVTME_MAX_BATCH_JOBS);
+        return fail(SVTME_ERR_BAD_PARAMETER, "%s: %u jobs (1..%d)", fn, n, SVTME_MAX_BATCH_JOBS);
     const uint32_t W = jobs[0].width, H = jobs[0].height;
     if (!W || !H || (W & 7) || (H & 7) || W > 16384 || H > 16384)
-        return fail(SVTME_ERR_BAD_PARAMETER, "svtme_tf_window: job size %ux%u must be a non-zero multiple of 8, "
-                                             "16384 at the most", W, H);
+        return fail(SVTME_ERR_BAD_PARAMETER, "%s: job size %ux%u must be a non-zero multiple of 8, "
+                                             "16384 at the most", fn, W, H);
     const uint32_t sbs = svtme_sb_total(W, H);
     for (uint32_t k = 0; k < n; k++) {
         const svtme_job &j = jobs[k];
         if (j.me_type != SVTME_ME_MCTF || j.num_lists != 1 || j.num_refs[0] != 1)
             return fail(SVTME_ERR_BAD_PARAMETER,
-                        "svtme_tf_window: job %u: me_type %u, %u lists, %u references (SVTME_ME_MCTF, one list, one "
-                        "reference)", k, j.me_type, j.num_lists, j.num_refs[0]);
+                        "%s: job %u: me_type %u, %u lists, %u references (SVTME_ME_MCTF, one list, one "
+                        "reference)", fn, k, j.me_type, j.num_lists, j.num_refs[0]);
         if (j.picture_number != jobs[0].picture_number)
-            return fail(SVTME_ERR_BAD_PARAMETER, "svtme_tf_window: job %u's centre is picture %llu, job 0's %llu", k,
+            return fail(SVTME_ERR_BAD_PARAMETER, "%s: job %u's centre is picture %llu, job 0's %llu", fn, k,
                         (unsigned long long)j.picture_number, (unsigned long long)jobs[0].picture_number);
         if (j.width != W || j.height != H)
-            return fail(SVTME_ERR_BAD_PARAMETER, "svtme_tf_window: job %u is %ux%u, job 0 %ux%u", k, j.width, j.height,
+            return fail(SVTME_ERR_BAD_PARAMETER, "%s: job %u is %ux%u, job 0 %ux%u", fn, k, j.width, j.height,
                         W, H);
         if (j.sb_begin != 0 || (j.sb_count != 0 && j.sb_count != sbs))
-            return fail(SVTME_ERR_BAD_PARAMETER, "svtme_tf_window: job %u covers SBs [%u, %u) of %u: the whole picture "
-                                                 "only", k, j.sb_begin, j.sb_begin + j.sb_count, sbs);
+            return fail(SVTME_ERR_BAD_PARAMETER, "%s: job %u covers SBs [%u, %u) of %u: the whole picture "
+                                                 "only", fn, k, j.sb_begin, j.sb_begin + j.sb_count, sbs);
     }
     if (!src_width || !src_height || svtme_align8_u(src_width) != W || svtme_align8_u(src_height) != H)
-        return fail(SVTME_ERR_BAD_PARAMETER, "svtme_tf_window: source size %ux%u does not align to the jobs' %ux%u",
+        return fail(SVTME_ERR_BAD_PARAMETER, "%s: source size %ux%u does not align to the jobs' %ux%u", fn,
                     src_width, src_height, W, H);
     if (out && out->plane && out->plane_stride < src_width)
-        return fail(SVTME_ERR_BAD_PARAMETER, "svtme_tf_window: plane_stride %u under the width %u", out->plane_stride,
+        return fail(SVTME_ERR_BAD_PARAMETER, "%s: plane_stride %u under the width %u", fn, out->plane_stride,
                     src_width);
+    if (uv && chroma_strides_ok(fn, uv, src_width))
+        return SVTME_ERR_BAD_PARAMETER;
     if (!tfsp_controls_ok(sp_ctl))
         return fail(SVTME_ERR_BAD_PARAMETER,
-                    "svtme_tf_window: sub-pel controls out of range: half %u quarter %u (0..3), eighth %u, use_2tap %u, "
-                    "sub_sampling_shift %u, enable_8x8_pred %u (0..1)",
+                    "%s: sub-pel controls out of range: half %u quarter %u (0..3), eighth %u, use_2tap %u, "
+                    "sub_sampling_shift %u, enable_8x8_pred %u (0..1)", fn,
                     sp_ctl->half_pel_mode, sp_ctl->quarter_pel_mode, sp_ctl->eight_pel_mode, sp_ctl->use_2tap,
                     sp_ctl->sub_sampling_shift, sp_ctl->enable_8x8_pred);
     if (!tff_controls_ok(f_ctl))
         return fail(SVTME_ERR_BAD_PARAMETER,
-                    "svtme_tf_window: filter controls out of range: tf_mv_dist_th %u (0..32767), sub_sampling_shift %u "
-                    "(0..1)", f_ctl->tf_mv_dist_th, f_ctl->sub_sampling_shift);
+                    "%s: filter controls out of range: tf_mv_dist_th %u (0..32767), sub_sampling_shift %u "
+                    "(0..1)", fn, f_ctl->tf_mv_dist_th, f_ctl->sub_sampling_shift);
     const uint64_t cen_pn = jobs[0].picture_number;
     for (uint32_t k = 0; k < n; k++)
         if (jobs[k].ref_picture_number[0][0] == out_pn)
-            return fail(SVTME_ERR_BAD_PARAMETER, "svtme_tf_window: the result picture %llu is job %u's reference",
+            return fail(SVTME_ERR_BAD_PARAMETER, "%s: the result picture %llu is job %u's reference", fn,
                         (unsigned long long)out_pn, k);
     std::lock_guard<std::mutex> lk(c->mu);
     for (uint32_t k = 0; k <= n; k++) { // (the batch checks the same; here before the result picture is made)
         const uint64_t pn = k ? jobs[k - 1].ref_picture_number[0][0] : cen_pn;
         auto it           = c->pics.find(pn);
         if (it == c->pics.end())
-            return fail(SVTME_ERR_BAD_PARAMETER, "svtme_tf_window: picture %llu is not resident", (unsigned long long)pn);
+            return fail(SVTME_ERR_BAD_PARAMETER, "%s: picture %llu is not resident", fn, (unsigned long long)pn);
         if (it->second.W != W || it->second.H != H)
-            return fail(SVTME_ERR_BAD_PARAMETER, "svtme_tf_window: picture %llu is %ux%u, the window %ux%u",
+            return fail(SVTME_ERR_BAD_PARAMETER, "%s: picture %llu is %ux%u, the window %ux%u", fn,
                         (unsigned long long)pn, it->second.W, it->second.H, W, H);
+        if (uv && !it->second.cmem)
+            return fail(SVTME_ERR_BAD_PARAMETER, "%s: picture %llu has no chroma", fn, (unsigned long long)pn);
     }
     HIP_TRY(hipSetDevice(c->device));
     // the sub-pel scratch holds the records (its results go to the filter's scratch), the filter's
-    // scratch the results of the sub-pel stage | tiles | weights | errors (no dense plane)
+    // scratch the results of the sub-pel stage | tiles | weights | errors (no dense plane), with chroma
+    // then its tiles | weights
     const size_t units = (size_t)n * sbs;
     const size_t rec_bytes = sizeof(svtme_ref_record) * units, sub_bytes = sizeof(svtme_tf_subpel_sb) * units,
                  tile_bytes = 4096 * units, wgt_bytes = 64 * units, e32_bytes = 16 * units;
     svtme_status st;
     if ((st = ensure_buf(&c->d_tfsp, &c->tfsp_cap, rec_bytes)) ||
-        (st = ensure_buf(&c->d_tff, &c->tff_cap, sub_bytes + tile_bytes + wgt_bytes + e32_bytes)))
+        (st = ensure_buf(&c->d_tff, &c->tff_cap,
+                         sub_bytes + tile_bytes + wgt_bytes + e32_bytes + (uv ? (2048 + 128) * units : 0))))
         return st;
     svtme_ref_record *d_rec   = (svtme_ref_record *)c->d_tfsp;
     uint8_t *base             = (uint8_t *)c->d_tff;
@@ -1914,7 +2151,7 @@ extern "C" svtme_status svtme_tf_window(svtme_ctx *c, const svtme_job *jobs, uin
         return st;
     // the result picture (a new number: a buffer of the pool; std::map keeps the others where they are)
     PicBuf *po;
-    if ((st = alloc_pic(c, out_pn, W, H, &po)))
+    if ((st = alloc_pic(c, out_pn, W, H, &po, uv != nullptr)) || (uv && (st = alloc_chroma(c, *po))))
         return st;
     PicBuf *pb[SVTME_MAX_BATCH_JOBS + 1];
     DevPlane ref[SVTME_MAX_BATCH_JOBS];
@@ -1928,11 +2165,24 @@ extern "C" svtme_status svtme_tf_window(svtme_ctx *c, const svtme_job *jobs, uin
     if ((st = join_upload(c, *po, 0)) || (st = after_readers(c, *po, L.s)))
         return st;
     HIP_TRY(svtme_launch_tfsp(&pb[0]->pyr.lv[0], ref, n, W, H, sp_ctl, d_rec, d_sub, L.s));
-    HIP_TRY(svtme_launch_tff_pic(&pb[0]->pyr.lv[0], ref, n, W, H, f_ctl, d_sub, d_tile, d_wgt, d_e32, &po->pyr.lv[0],
-                                 L.s));
+    if (uv) {
+        // both predictions before either normalisation: in place the chroma stage reads the centre's luma
+        TffcArgs U{};
+        tffc_fill(U, pb, n, W, H, f_ctl, uv, d_sub, d_tile, d_e32, (uint8_t *)d_e32 + e32_bytes);
+        U.dst[0] = po->chroma[0], U.dst[1] = po->chroma[1];
+        HIP_TRY(svtme_launch_tff_pic_yuv(&pb[0]->pyr.lv[0], ref, n, W, H, f_ctl, d_sub, d_tile, d_wgt, d_e32,
+                                         &po->pyr.lv[0], &U, L.s));
+    } else
+        HIP_TRY(svtme_launch_tff_pic(&pb[0]->pyr.lv[0], ref, n, W, H, f_ctl, d_sub, d_tile, d_wgt, d_e32,
+                                     &po->pyr.lv[0], L.s));
     // the sub-8 re-pad and the margins from the plane's own interior, then levels 1 and 2
     if ((st = build_pyramid(c, po, po->pyr.lv[0].base, (uint32_t)po->pyr.lv[0].stride, src_width, src_height, 0, L.s)))
         return st;
+    // the chroma planes likewise: beyond the true chroma size and the margins, from their own interior
+    for (int p = 0; uv && p < 2; p++)
+        if ((st = build_chroma(po, p, po->chroma[p].base, (uint32_t)po->chroma[p].stride, (src_width + 1) >> 1,
+                               (src_height + 1) >> 1, L.s)))
+            return st;
     hipEvent_t done = L.ev[L.ev_next];
     L.ev_next       = (L.ev_next + 1) % Lane::kEv;
     HIP_TRY(hipEventRecord(done, L.s));
@@ -1943,19 +2193,44 @@ extern "C" svtme_status svtme_tf_window(svtme_ctx *c, const svtme_job *jobs, uin
         HIP_TRY(hipEventCreateWithFlags(&po->ready, hipEventDisableTiming));
     HIP_TRY(hipEventRecord(po->ready, L.s));
     po->pending = ((1u << SVTME_LANES) - 1u) & ~1u;
-    if (!out || (!out->plane && !out->records && !out->subpel && !out->err32))
+    const bool want_uv = uv && (uv->out[0] || uv->out[1]);
+    if (!want_uv && (!out || (!out->plane && !out->records && !out->subpel && !out->err32)))
         return SVTME_OK;
-    if (out->records)
+    if (out && out->records)
         HIP_TRY(hipMemcpyAsync(out->records, d_rec, rec_bytes, hipMemcpyDeviceToHost, L.s));
-    if (out->subpel)
+    if (out && out->subpel)
         HIP_TRY(hipMemcpyAsync(out->subpel, d_sub, sub_bytes, hipMemcpyDeviceToHost, L.s));
-    if (out->err32)
+    if (out && out->err32)
         HIP_TRY(hipMemcpyAsync(out->err32, d_e32, e32_bytes, hipMemcpyDeviceToHost, L.s));
-    if (out->plane)
+    if (out && out->plane)
         HIP_TRY(hipMemcpy2DAsync(out->plane, out->plane_stride, po->pyr.lv[0].base, (size_t)po->pyr.lv[0].stride,
                                  src_width, src_height, hipMemcpyDeviceToHost, L.s));
+    for (int p = 0; want_uv && p < 2; p++)
+        if (uv->out[p])
+            HIP_TRY(hipMemcpy2DAsync(uv->out[p], uv->stride[p], po->chroma[p].base, (size_t)po->chroma[p].stride,
+                                     (src_width + 1) >> 1, (src_height + 1) >> 1, hipMemcpyDeviceToHost, L.s));
     HIP_TRY(hipStreamSynchronize(L.s));
     return SVTME_OK;
+}
+
+extern "C" svtme_status svtme_tf_window(svtme_ctx *c, const svtme_job *jobs, uint32_t n, uint32_t src_width,
+                                        uint32_t src_height, const svtme_tf_subpel_controls *sp_ctl,
+                                        const svtme_tf_filter_controls *f_ctl, uint64_t out_pn,
+                                        const svtme_tf_window_out *out) {
+    return tf_window_impl("svtme_tf_window", nullptr, c, jobs, n, src_width, src_height, sp_ctl, f_ctl, out_pn, out);
+}
+
+extern "C" svtme_status svtme_tf_window_yuv(svtme_ctx *c, const svtme_job *jobs, uint32_t n, uint32_t src_width,
+                                            uint32_t src_height, const svtme_tf_subpel_controls *sp_ctl,
+                                            const svtme_tf_filter_yuv_controls *f_ctl, uint64_t out_pn,
+                                            const svtme_tf_window_out *out, const svtme_tf_window_yuv_out *out_uv) {
+    if (!f_ctl)
+        return fail(SVTME_ERR_BAD_PARAMETER, "svtme_tf_window_yuv: null filter_controls");
+    const TfChroma uv = {{f_ctl->tf_decay_factor_cb_fp16, f_ctl->tf_decay_factor_cr_fp16},
+                         {out_uv ? out_uv->cb : nullptr, out_uv ? out_uv->cr : nullptr},
+                         {out_uv ? out_uv->cb_stride : 0, out_uv ? out_uv->cr_stride : 0}};
+    return tf_window_impl("svtme_tf_window_yuv", &uv, c, jobs, n, src_width, src_height, sp_ctl, &f_ctl->luma, out_pn,
+                          out);
 }
 
 extern "C" void *svtme_device_records(svtme_ctx *c, uint64_t *bytes) {

@@ -282,6 +282,37 @@ class TfWindowOut(C.Structure):
                 ("subpel", C.c_void_p), ("err32", C.c_void_p)]
 
 
+PAD_CHROMA = 40  # SVTME_PAD_CHROMA: the logical padding of a resident chroma plane
+
+
+class TfFilterYuvControls(C.Structure):
+    """svtme_tf_filter_yuv_controls: the luma controls and the two chroma decay factors."""
+    _fields_ = [("luma", TfFilterControls), ("tf_decay_factor_cb_fp16", C.c_uint32),
+                ("tf_decay_factor_cr_fp16", C.c_uint32)]
+
+    @staticmethod
+    def from_dict(d: dict) -> "TfFilterYuvControls":
+        """The keys of TfFilterControls plus tf_decay_factor_cb_fp16 and tf_decay_factor_cr_fp16."""
+        chroma = ("tf_decay_factor_cb_fp16", "tf_decay_factor_cr_fp16")
+        return TfFilterYuvControls(luma=TfFilterControls.from_dict({k: v for k, v in d.items() if k not in chroma}),
+                                   **{k: int(d[k]) for k in chroma})
+
+    def as_dict(self) -> dict:
+        return dict(self.luma.as_dict(), tf_decay_factor_cb_fp16=int(self.tf_decay_factor_cb_fp16),
+                    tf_decay_factor_cr_fp16=int(self.tf_decay_factor_cr_fp16))
+
+
+class TfFilterYuvOut(C.Structure):
+    """svtme_tf_filter_yuv_out: where svtme_tf_filter_yuv writes; cb, cr and err32 may be NULL."""
+    _fields_ = [("y", C.c_void_p), ("cb", C.c_void_p), ("cr", C.c_void_p), ("y_stride", C.c_uint32),
+                ("cb_stride", C.c_uint32), ("cr_stride", C.c_uint32), ("pad", C.c_uint32), ("err32", C.c_void_p)]
+
+
+class TfWindowYuvOut(C.Structure):
+    """svtme_tf_window_yuv_out: host copies of a window's filtered chroma, each pointer NULL or a buffer."""
+    _fields_ = [("cb", C.c_void_p), ("cr", C.c_void_p), ("cb_stride", C.c_uint32), ("cr_stride", C.c_uint32)]
+
+
 TAIL_BYTES = 24  # svtme_record_tail: the last 24 bytes of svtme_ref_record
 
 
@@ -736,6 +767,20 @@ def _job_api_protos(lib):
                                                     C.POINTER(TfSubpelControls), C.POINTER(TfFilterControls),
                                                     C.c_uint64, C.POINTER(TfWindowOut)])
         _proto(lib, "svtme_tf_window", "restype", C.c_int32)
+        _proto(lib, "svtme_picture_upload_chroma", "argtypes", [vp, C.c_uint64, vp, vp, C.c_uint32, C.c_uint32,
+                                                                C.c_uint32])
+        _proto(lib, "svtme_picture_upload_chroma", "restype", C.c_int32)
+        _proto(lib, "svtme_picture_download_chroma", "argtypes", [vp, C.c_uint64, C.c_int, vp] +
+               [C.POINTER(C.c_uint32)] * 4)
+        _proto(lib, "svtme_picture_download_chroma", "restype", C.c_int32)
+        _proto(lib, "svtme_tf_filter_yuv", "argtypes", [vp, C.c_uint64, C.POINTER(C.c_uint64), C.c_uint32, C.c_uint32,
+                                                        C.c_uint32, C.POINTER(TfFilterYuvControls), vp,
+                                                        C.POINTER(TfFilterYuvOut)])
+        _proto(lib, "svtme_tf_filter_yuv", "restype", C.c_int32)
+        _proto(lib, "svtme_tf_window_yuv", "argtypes", [vp, C.POINTER(Job), C.c_uint32, C.c_uint32, C.c_uint32,
+                                                        C.POINTER(TfSubpelControls), C.POINTER(TfFilterYuvControls),
+                                                        C.c_uint64, C.POINTER(TfWindowOut), C.POINTER(TfWindowYuvOut)])
+        _proto(lib, "svtme_tf_window_yuv", "restype", C.c_int32)
         lib._svtme_protos = True
     return lib
 
@@ -847,6 +892,27 @@ class GpuME:
         self._check(self.lib.svtme_picture_download(self.ctx, picture_number, level, out.ctypes.data,
                                                     C.byref(stride), C.byref(w), C.byref(h), C.byref(pad)),
                     "svtme_picture_download")
+        return out
+
+    def upload_chroma(self, picture_number: int, cb: np.ndarray, cr: np.ndarray, width: int, height: int):
+        """svtme_picture_upload_chroma: attach 8-bit 4:2:0 chroma to the resident picture; width x height
+        is the luma source size, cb and cr hold ((height + 1) >> 1, (width + 1) >> 1) samples."""
+        cb, cr = np.ascontiguousarray(cb, np.uint8), np.ascontiguousarray(cr, np.uint8)
+        shape = ((height + 1) >> 1, (width + 1) >> 1)
+        if cb.shape != shape or cr.shape != shape:
+            raise ValueError(f"chroma planes {cb.shape}, {cr.shape} for a {width}x{height} picture ({shape})")
+        self._check(self.lib.svtme_picture_upload_chroma(self.ctx, picture_number, cb.ctypes.data, cr.ctypes.data,
+                                                         shape[1], width, height), "svtme_picture_upload_chroma")
+
+    def download_chroma(self, picture_number: int, plane: int) -> np.ndarray:
+        """svtme_picture_download_chroma: plane 1 (Cb) or 2 (Cr) with its margins, (H/2 + 80, W/2 + 80)."""
+        stride, w, h, pad = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32()
+        args = (C.byref(stride), C.byref(w), C.byref(h), C.byref(pad))
+        self._check(self.lib.svtme_picture_download_chroma(self.ctx, picture_number, plane, None, *args),
+                    "svtme_picture_download_chroma")
+        out = np.empty((h.value + 2 * pad.value, stride.value), np.uint8)
+        self._check(self.lib.svtme_picture_download_chroma(self.ctx, picture_number, plane, out.ctypes.data, *args),
+                    "svtme_picture_download_chroma")
         return out
 
     def submit(self, job: Job, with_sb_results: bool = True):
@@ -1042,6 +1108,64 @@ class GpuME:
                                              C.byref(filter_controls), int(out_pn), C.byref(out) if res else None),
                     "svtme_tf_window")
         return res
+
+    def tf_filter_yuv(self, centre: int, refs, width: int, height: int, controls: TfFilterYuvControls,
+                      subpel: np.ndarray, with_err32: bool = True, want=("cb", "cr"), strides=None):
+        """svtme_tf_filter_yuv: tf_filter with the chroma stage -> (y [height, width], cb, cr
+        [(height + 1) >> 1, (width + 1) >> 1] u8 or None where not in `want`, err32 or None).
+        strides: (y, cb, cr) row distances; the planes are then views of rows that far apart."""
+        n = len(refs)
+        sbs = sb_total(align8(width), align8(height))
+        subpel = np.ascontiguousarray(subpel, TF_SUBPEL_SB_DTYPE)
+        if subpel.size != n * sbs:
+            raise ValueError(f"{subpel.size} sub-pel results for {n} references x {sbs} SBs")
+        arr = (C.c_uint64 * max(n, 1))(*[int(r) for r in refs])
+        cw, ch = (width + 1) >> 1, (height + 1) >> 1
+        sy, scb, scr = strides or (width, cw, cw)
+        y = np.zeros((height, sy), np.uint8)
+        cb = np.zeros((ch, scb), np.uint8) if "cb" in want else None
+        cr = np.zeros((ch, scr), np.uint8) if "cr" in want else None
+        err32 = np.zeros((n, sbs, 4), np.uint32) if with_err32 else None
+        out = TfFilterYuvOut(y=y.ctypes.data, cb=cb.ctypes.data if cb is not None else None,
+                             cr=cr.ctypes.data if cr is not None else None, y_stride=sy, cb_stride=scb,
+                             cr_stride=scr, err32=err32.ctypes.data if with_err32 else None)
+        self._check(self.lib.svtme_tf_filter_yuv(self.ctx, int(centre), arr, n, width, height, C.byref(controls),
+                                                 subpel.ctypes.data, C.byref(out)), "svtme_tf_filter_yuv")
+        return (y[:, :width], cb[:, :cw] if cb is not None else None, cr[:, :cw] if cr is not None else None,
+                err32)
+
+    def tf_window_yuv(self, jobs, src_w: int, src_h: int, subpel_controls: TfSubpelControls,
+                      filter_controls: TfFilterYuvControls, out_pn: int,
+                      want=("plane", "records", "subpel", "err32", "cb", "cr")):
+        """svtme_tf_window_yuv: tf_window with the chroma stage; the result picture `out_pn` gets the
+        filtered chroma planes too. -> {name: array} of the outputs named in `want`: tf_window's, and
+        cb, cr [(src_h + 1) >> 1, (src_w + 1) >> 1] u8."""
+        unknown = set(want) - {"plane", "records", "subpel", "err32", "cb", "cr"}
+        if unknown:
+            raise ValueError(f"unknown outputs {sorted(unknown)}")
+        n = len(jobs)
+        arr = (Job * max(n, 1))(*jobs)
+        sbs = sb_total(align8(src_w), align8(src_h))
+        cw, ch = (src_w + 1) >> 1, (src_h + 1) >> 1
+        res, uv = {}, {}
+        if "plane" in want:
+            res["plane"] = np.zeros((src_h, src_w), np.uint8)
+        if "records" in want:
+            res["records"] = np.zeros((n, sbs), REF_RECORD_DTYPE)
+        if "subpel" in want:
+            res["subpel"] = np.zeros((n, sbs), TF_SUBPEL_SB_DTYPE)
+        if "err32" in want:
+            res["err32"] = np.zeros((n, sbs, 4), np.uint32)
+        for name in ("cb", "cr"):
+            if name in want:
+                uv[name] = np.zeros((ch, cw), np.uint8)
+        out = TfWindowOut(plane_stride=src_w, **{k: v.ctypes.data for k, v in res.items()})
+        out_uv = TfWindowYuvOut(cb_stride=cw, cr_stride=cw, **{k: v.ctypes.data for k, v in uv.items()})
+        self._check(self.lib.svtme_tf_window_yuv(self.ctx, arr, n, src_w, src_h, C.byref(subpel_controls),
+                                                 C.byref(filter_controls), int(out_pn),
+                                                 C.byref(out) if res else None, C.byref(out_uv) if uv else None),
+                    "svtme_tf_window_yuv")
+        return dict(res, **uv)
 
     def device_records(self):
         n = C.c_uint64()
