@@ -15,8 +15,8 @@ T=$(mktemp -d)
 trap 'rm -rf "$T"' EXIT
 FL="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall"
 /opt/rocm/bin/hipcc $FL -include $C/diag/svtme_diag.h "$@" -c -o $T/stages.o $C/svtme_stages.hip
-for f in svtme_pyramid.hip svtme_pack.hip svtme_rtcd.hip svtme_dg.hip svtme_tfsp.hip svtme_host.cpp; do
-  /opt/rocm/bin/hipcc $FL -c -o $T/$f.o $C/$f
+for f in $C/*.hip $C/*.cpp; do  # every product source: no list to fall behind
+  [ "$f" = $C/svtme_stages.hip ] || /opt/rocm/bin/hipcc $FL -c -o $T/$(basename $f).o $f
 done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o svt-av1-mirror_amd/libsvtme_$NAME.so $T/*.o
 echo "built svt-av1-mirror_amd/libsvtme_$NAME.so ($*)"

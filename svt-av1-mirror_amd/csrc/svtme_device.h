@@ -1,6 +1,7 @@
 // svtme_device.h — device-side layouts shared by the HIP kernels and the host
 // launcher (svtme_host.cpp). gfx950 (MI355X) only.
 #pragma once
+#include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/svtme.h"
@@ -116,6 +117,75 @@ struct DevBatch {
     uint32_t total; // units of this launch
     uint32_t start[SVTME_MAX_BATCH];
 };
+
+// Stage-A search kinds (DevJob.ta_list / ta1_list entries are kind << 3 | slot): written by the
+// host's stage lists (svtme_dispatch.cpp), read by k_stage_a and k_l0_full.
+#define TA_HME 0   // zz SAD + the four HME-L0 quadrants of one slot
+#define TA_PH 1    // the two pre-HME regions of one slot
+#define TA_ZZ 2    // zz SAD only (real-time tune, slots 1-7: their HME-L0 waits for slot 0's)
+#define TA_L0RT 3  // the four HME-L0 quadrants with the area k_stage_d<true> left in BState
+
+// LDS row geometry of k_fp_wide that the host's svtme_fp_wide_lds tests an area against.
+#define FPW_BOFF 40  // fw_b within the row: one base address serves both copies
+#define FPW_TQ 4 // position quads per set (2 quad pairs, 16 positions; 6 wastes a third of the
+                 // last set at 64 positions, 8 measures the same as 4)
+// svtme_fp_wide_lds admits 14 + nsets * FPW_TQ + 3 <= FPW_BOFF; k_fp_wide codes a record's set
+// in 8 bits (rc & 0xFF), so that bound must keep nsets below 256
+static_assert((FPW_BOFF - 14 - 3) / FPW_TQ < 256, "k_fp_wide's 8-bit set code holds every nsets svtme_fp_wide_lds admits");
+
+// Search parameters the host's dispatch and the kernels derive alike (pure).
+#define SVTME_HD __host__ __device__ __forceinline__
+namespace svtme {
+SVTME_HD int16_t i16(int v) { return (int16_t)v; }
+SVTME_HD int absi(int v) { return v < 0 ? -v : v; }
+SVTME_HD int imin(int a, int b) { return a < b ? a : b; }
+SVTME_HD uint32_t min_u32(uint32_t a, uint32_t b) { return a < b ? a : b; }
+SVTME_HD uint64_t min_u64(uint64_t a, uint64_t b) { return a < b ? a : b; }
+
+// motion_estimation.c:1239-1243
+SVTME_HD uint16_t scaled_dist(uint16_t dist) {
+    uint8_t round_up = ((dist % 8) == 0) ? 0 : 1;
+    return (uint16_t)(((dist * 5) / 8) + round_up);
+}
+SVTME_HD uint16_t ref_dist_const(const svtme_job &j, int l, int r) {
+    int64_t d = (int64_t)j.picture_number - (int64_t)j.ref_picture_number[l][r];
+    return (uint16_t)(int16_t)(d < 0 ? -d : d);
+}
+
+// get_hme_l0_search_area (motion_estimation.c:1800-1867); the per-ref
+// mutate/restore of hme_l0_sa makes it a function of (list, ref, dist)
+SVTME_HD void hme_l0_area(const svtme_controls &c, int l, int r, uint16_t dist, int16_t l00x, int16_t l00y,
+                          int16_t *sa_w, int16_t *sa_h) {
+    uint32_t mnw = c.hme_l0_sa.sa_min.width, mnh = c.hme_l0_sa.sa_min.height;
+    uint32_t mxw = c.hme_l0_sa.sa_max.width, mxh = c.hme_l0_sa.sa_max.height;
+    if (c.enable_me_sr_adjustment && c.distance_based_hme_resizing) {
+        uint8_t is_hor = 1, is_ver = 1, is_still = 0;
+        if (c.reduce_hme_l0_sr_th_min && c.reduce_hme_l0_sr_th_max && (l || r)) {
+            const int mvx = l00x, mvy = l00y;
+            is_ver   = (absi(mvx) < c.reduce_hme_l0_sr_th_min) && (absi(mvy) > c.reduce_hme_l0_sr_th_max);
+            is_hor   = (absi(mvx) > c.reduce_hme_l0_sr_th_max) && (absi(mvy) < c.reduce_hme_l0_sr_th_min);
+            is_still = (absi(mvx) < (c.reduce_hme_l0_sr_th_min * 3)) && (absi(mvy) < (c.reduce_hme_l0_sr_th_min * 3));
+        }
+        uint8_t xo = 1, yo = 1;
+        if (!is_ver)
+            yo = 2;
+        if (!is_hor)
+            xo = 2;
+        if (c.enable_me_sr_adjustment == 2 && is_still)
+            xo = yo = 4;
+        mnw = (uint16_t)(mnw / (xo + r));
+        mnh = (uint16_t)(mnh / (yo + r));
+        mxw = (uint16_t)(mxw / (xo + r));
+        mxh = (uint16_t)(mxh / (yo + r));
+    }
+    const int32_t f = scaled_dist(dist);
+    int16_t w       = i16(mnw / c.num_hme_sa_w);
+    w               = i16(imin((((w * f) + 15) & ~0x0F), (int)(((mxw / c.num_hme_sa_w) + 15) & ~0x0F)));
+    int16_t h       = i16(mnh / c.num_hme_sa_h);
+    h               = i16(imin((h * f), (int)(mxh / c.num_hme_sa_h)));
+    *sa_w = w, *sa_h = h;
+}
+} // namespace svtme
 
 static inline uint32_t svtme_round_up(uint32_t v, uint32_t a) { return (v + a - 1) / a * a; }
 static inline uint32_t svtme_align8_u(uint32_t v) { return (v + 7u) & ~7u; }

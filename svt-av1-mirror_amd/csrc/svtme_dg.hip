@@ -29,6 +29,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "svtme_launch.h"
 #include "svtme_me_common.h"
 
 using namespace svtme;

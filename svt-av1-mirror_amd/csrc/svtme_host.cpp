@@ -25,53 +25,7 @@
 #include <string>
 #include <vector>
 
-#include "svtme_device.h"
-
-extern "C" hipError_t svtme_launch_build_full(const void *src, uint32_t src_stride, int w, int h, int ten_bit,
-                                              DevPlane dst, int left, int top, int rows, hipStream_t s);
-extern "C" hipError_t svtme_launch_copy_words(const void *src, void *dst, uint32_t nwords, hipStream_t s);
-extern "C" hipError_t svtme_launch_pack(const svtme_ref_record *d_recs, const svtme_sb_result *d_sb, uint32_t n_sb,
-                                        uint32_t R, const svtme_pack_layout *L, void *d_out, hipStream_t s);
-extern "C" hipError_t svtme_launch_build_down(DevPlane prev, DevPlane dst, int left, int top, int rows,
-                                              hipStream_t s);
-extern "C" hipError_t svtme_launch_stages(const DevJob *d_jobs, const DevJob *h_jobs, uint32_t n, hipStream_t s,
-                                          hipEvent_t *ev, uint32_t *mask);
-extern "C" uint32_t svtme_launch_key(const DevJob *dj);
-extern "C" hipError_t svtme_prime_pyramid(void);
-extern "C" hipError_t svtme_launch_host_rows(const uint8_t *src, uint32_t src_stride, int w, int h, uint8_t *dst,
-                                             uint32_t dst_stride, hipStream_t s);
-extern "C" hipError_t svtme_prime_pack(void);
-extern "C" hipError_t svtme_prime_stages(void);
-extern "C" hipError_t svtme_prime_dg(void);
-extern "C" hipError_t svtme_launch_dg(const DevPlane *cur, const DevPlane *ref, uint32_t n, uint32_t width,
-                                      uint32_t height, uint16_t sa_w, uint16_t sa_h, svtme_dg_metrics *d_acc,
-                                      svtme_dg_sb *d_sb, hipStream_t s);
-extern "C" hipError_t svtme_prime_tfsp(void);
-extern "C" hipError_t svtme_launch_tfsp(const DevPlane *cen, const DevPlane *ref, uint32_t n, uint32_t width,
-                                        uint32_t height, const svtme_tf_subpel_controls *ctl,
-                                        const svtme_ref_record *d_rec, svtme_tf_subpel_sb *d_out, hipStream_t s);
-extern "C" hipError_t svtme_prime_tff(void);
-extern "C" hipError_t svtme_launch_tff(const DevPlane *cen, const DevPlane *ref, uint32_t n, uint32_t width,
-                                       uint32_t height, const svtme_tf_filter_controls *ctl,
-                                       const svtme_tf_subpel_sb *d_sub, uint8_t *d_tile, uint32_t *d_wgt,
-                                       uint32_t *d_e32, uint8_t *d_plane, hipStream_t s);
-extern "C" hipError_t svtme_launch_tffc(const TffcArgs *A, hipStream_t s);
-extern "C" hipError_t svtme_launch_tff_pic_yuv(const DevPlane *cen, const DevPlane *ref, uint32_t n, uint32_t width,
-                                               uint32_t height, const svtme_tf_filter_controls *ctl,
-                                               const svtme_tf_subpel_sb *d_sub, uint8_t *d_tile, uint32_t *d_wgt,
-                                               uint32_t *d_e32, const DevPlane *dst, const TffcArgs *U, hipStream_t s);
-extern "C" hipError_t svtme_launch_tff_pic(const DevPlane *cen, const DevPlane *ref, uint32_t n, uint32_t width,
-                                           uint32_t height, const svtme_tf_filter_controls *ctl,
-                                           const svtme_tf_subpel_sb *d_sub, uint8_t *d_tile, uint32_t *d_wgt,
-                                           uint32_t *d_e32, const DevPlane *dst, hipStream_t s);
-extern "C" void svtme_stage_a_list(const svtme_job *job, uint8_t *list, uint32_t *count);
-extern "C" void svtme_stage_b_list(const svtme_job *job, uint8_t *list, uint32_t *count);
-extern "C" void svtme_stage_a1_list(const svtme_job *job, uint8_t *list, uint32_t *count);
-extern "C" uint32_t svtme_fp_parts_paths(const svtme_controls *c, uint32_t paths);
-extern "C" void svtme_fp_area_bound(const svtme_controls *c, uint32_t *w, uint32_t *h);
-extern "C" void svtme_hme_prepare(DevJob *dj);
-extern "C" bool svtme_hme_fused(const svtme_job *job);
-extern "C" bool svtme_hme_rt(const svtme_controls *c);
+#include "svtme_launch.h"
 
 // ----------------------------------------------------------------------------
 // errors
@@ -1261,7 +1215,7 @@ static svtme_status submit_batch_locked(svtme_ctx *c, const svtme_job *jobs, uin
         return st;
     bool any_banded = false, any_single = false, any_wide = false;
     for (uint32_t k = 0; k < n; k++) {
-        hj[k].parts = svtme_fp_parts_paths(&hj[k].job.ctrl, hj[k].paths);
+        svtme_plan_job(&hj[k]);
         any_wide |= hj[k].parts != 0;
         any_banded |= hj[k].parts > 1;
         any_single |= hj[k].parts == 1;
@@ -1289,10 +1243,6 @@ static svtme_status submit_batch_locked(svtme_ctx *c, const svtme_job *jobs, uin
         hj[k].bst   = L.d_bst + sb_off;
         hj[k].keys  = hj[k].parts ? L.d_keys + slot_off * SVTME_PU_COUNT : nullptr;
         hj[k].cslot = hj[k].parts ? L.d_cslot + slot_off : nullptr;
-        svtme_stage_a_list(&hj[k].job, hj[k].ta_list, &hj[k].ta_count);
-        svtme_stage_a1_list(&hj[k].job, hj[k].ta1_list, &hj[k].ta1_count);
-        svtme_stage_b_list(&hj[k].job, hj[k].tb_list, &hj[k].tb_count);
-        svtme_hme_prepare(&hj[k]);
         sb_off += count[k];
         slot_off += (size_t)count[k] * hj[k].R;
     }

@@ -11,22 +11,6 @@
 
 namespace svtme {
 
-#define SVTME_HD __host__ __device__ __forceinline__
-SVTME_HD int16_t i16(int v) { return (int16_t)v; }
-SVTME_HD int absi(int v) { return v < 0 ? -v : v; }
-SVTME_HD int imin(int a, int b) { return a < b ? a : b; }
-SVTME_HD uint32_t min_u32(uint32_t a, uint32_t b) { return a < b ? a : b; }
-SVTME_HD uint64_t min_u64(uint64_t a, uint64_t b) { return a < b ? a : b; }
-
-// motion_estimation.c:1239-1243
-SVTME_HD uint16_t scaled_dist(uint16_t dist) {
-    uint8_t round_up = ((dist % 8) == 0) ? 0 : 1;
-    return (uint16_t)(((dist * 5) / 8) + round_up);
-}
-SVTME_HD uint16_t ref_dist_const(const svtme_job &j, int l, int r) {
-    int64_t d = (int64_t)j.picture_number - (int64_t)j.ref_picture_number[l][r];
-    return (uint16_t)(int16_t)(d < 0 ? -d : d);
-}
 // A wave-uniform byte / halfword field of a struct (a job) in global memory, read
 // as the dword that holds it: a scalar load (gfx950 has no scalar sub-dword load,
 // so the field itself would be a vector-memory round trip). SF(job, max_l0).
@@ -238,40 +222,6 @@ __device__ void hme_refine_rect(int level, const DevPlane &p, int16_t org_x, int
     if ((org_y + oy + sa_h) > ph)
         sa_h = i16(max(1, sa_h - ((org_y + oy + sa_h) - ph)));
     *oxo = ox, *oyo = oy, *saw = sa_w, *sah = sa_h;
-}
-
-// get_hme_l0_search_area (motion_estimation.c:1800-1867); the per-ref
-// mutate/restore of hme_l0_sa makes it a function of (list, ref, dist)
-SVTME_HD void hme_l0_area(const svtme_controls &c, int l, int r, uint16_t dist, int16_t l00x, int16_t l00y,
-                          int16_t *sa_w, int16_t *sa_h) {
-    uint32_t mnw = c.hme_l0_sa.sa_min.width, mnh = c.hme_l0_sa.sa_min.height;
-    uint32_t mxw = c.hme_l0_sa.sa_max.width, mxh = c.hme_l0_sa.sa_max.height;
-    if (c.enable_me_sr_adjustment && c.distance_based_hme_resizing) {
-        uint8_t is_hor = 1, is_ver = 1, is_still = 0;
-        if (c.reduce_hme_l0_sr_th_min && c.reduce_hme_l0_sr_th_max && (l || r)) {
-            const int mvx = l00x, mvy = l00y;
-            is_ver   = (absi(mvx) < c.reduce_hme_l0_sr_th_min) && (absi(mvy) > c.reduce_hme_l0_sr_th_max);
-            is_hor   = (absi(mvx) > c.reduce_hme_l0_sr_th_max) && (absi(mvy) < c.reduce_hme_l0_sr_th_min);
-            is_still = (absi(mvx) < (c.reduce_hme_l0_sr_th_min * 3)) && (absi(mvy) < (c.reduce_hme_l0_sr_th_min * 3));
-        }
-        uint8_t xo = 1, yo = 1;
-        if (!is_ver)
-            yo = 2;
-        if (!is_hor)
-            xo = 2;
-        if (c.enable_me_sr_adjustment == 2 && is_still)
-            xo = yo = 4;
-        mnw = (uint16_t)(mnw / (xo + r));
-        mnh = (uint16_t)(mnh / (yo + r));
-        mxw = (uint16_t)(mxw / (xo + r));
-        mxh = (uint16_t)(mxh / (yo + r));
-    }
-    const int32_t f = scaled_dist(dist);
-    int16_t w       = i16(mnw / c.num_hme_sa_w);
-    w               = i16(imin((((w * f) + 15) & ~0x0F), (int)(((mxw / c.num_hme_sa_w) + 15) & ~0x0F)));
-    int16_t h       = i16(mnh / c.num_hme_sa_h);
-    h               = i16(imin((h * f), (int)(mxh / c.num_hme_sa_h)));
-    *sa_w = w, *sa_h = h;
 }
 
 // ----------------------------------------------------------------------------

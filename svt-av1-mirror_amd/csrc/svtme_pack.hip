@@ -11,7 +11,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#include "svtme_device.h"
+#include "svtme_launch.h"
 
 #define PACK_MAX_BYTES 12288 // >= svtme_packed_sb_bytes of the largest layout (R = 8, full records, 85 PUs)
 

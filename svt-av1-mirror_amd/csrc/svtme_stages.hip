@@ -32,9 +32,8 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include "svtme_launch.h"
 #include "svtme_me_common.h"
-
-extern "C" bool svtme_hme_rt(const svtme_controls *c); // (host dispatch, end of file)
 
 namespace svtme {
 
@@ -432,11 +431,7 @@ __device__ __forceinline__ uint32_t zz_finish(const ZzLoads &z) {
     return wave_sum_u32(acc);
 }
 
-// Stage A wave kinds (DevJob.ta_list entry = kind << 3 | slot)
-#define TA_HME 0   // zz SAD + the four HME-L0 quadrants of one slot
-#define TA_PH 1    // the two pre-HME regions of one slot
-#define TA_ZZ 2    // zz SAD only (real-time tune, slots 1-7: their HME-L0 waits for slot 0's)
-#define TA_L0RT 3  // the four HME-L0 quadrants with the area k_stage_d<true> left in BState
+// (the stage-A wave kinds TA_HME, TA_PH, TA_ZZ, TA_L0RT: svtme_device.h)
 
 template <bool R1> // R1: the real-time tune's second round (DevJob.ta1_list)
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) k_stage_a(const DevBatch B) {
@@ -2966,10 +2961,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SUB ? 
 #define FPW_PITCH 80 // dwords per LDS row (fw_a then fw_b): the two search rows (hr = 0, 1) of one by2
                      // fall on banks 0-15 / 16-31; the other by2 of a 32-lane ds_read_b64 group reads
                      // rows 16 further (16 x 80 = 0 mod 64 banks): a 2-way conflict
-#define FPW_BOFF 40  // fw_b within the row: one base address serves both copies
 #define FPW_ROWS 96  // window rows per workgroup (4 bands + 62; the host bounds the band height)
-#define FPW_TQ 4 // position quads per set (2 quad pairs, 16 positions; 6 wastes a third of the
-               // last set at 64 positions, 8 measures the same as 4)
+// (FPW_BOFF, fw_b within the row, and FPW_TQ, the position quads per set: svtme_device.h)
 
 struct FpW {
     uint32_t b8t, b8b, b16, b32, b64; // K32 keys: 8x8 / 16x16 (sad << 16 | order), 32x32 / 64x64 (sad << 12 | order)
@@ -4742,248 +4735,31 @@ __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(HM
 
 } // namespace svtme
 
-// Stage-A search list of a job: every independent search the reference may
-// perform for a valid slot (see k_stage_a). Host-side, pure.
-extern "C" void svtme_stage_a_list(const svtme_job *job, uint8_t *list, uint32_t *count) {
-    const svtme_controls &c = job->ctrl;
-    uint32_t n = 0;
-    for (int s = 0; s < 8; s++) {
-        const int l = s >> 2, r = s & 3;
-        if (l >= job->num_lists || r >= job->num_refs[l])
-            continue;
-        if (!(job->temporal_layer_index > 0 || l == 0))
-            continue;
-        const bool zz = c.me_early_exit_th || c.me_safe_limit_zz_th;
-        const bool l0 = c.enable_hme_flag && c.enable_hme_level0_flag;
-        if (svtme_hme_rt(&c) && s > 0) { // HME-L0 in the second round (svtme_stage_a1_list)
-            if (zz)
-                list[n++] = (uint8_t)((TA_ZZ << 3) | s);
-        } else if (zz || l0)
-            list[n++] = (uint8_t)((TA_HME << 3) | s);
-        if (c.prehme_enable)
-            list[n++] = (uint8_t)((TA_PH << 3) | s);
+// The launch table: one row per KernelId (svtme_launch.h). Which of them a job runs is decided
+// in svtme_dispatch.cpp (svtme_launch_plan); nothing below evaluates a dispatch predicate.
+struct StageKernel {
+    void (*fn)(const DevBatch);
+    uint16_t threads; // workgroup size
+    uint8_t per_wg;   // work units per workgroup
+};
+static const StageKernel kStageKernels[K_COUNT] = {
+    {nullptr, 0, 0},
+#define SVTME_X(id, nt, units, per_wg, ...) {svtme::__VA_ARGS__, nt, per_wg},
+    SVTME_STAGE_KERNELS(SVTME_X)
+#undef SVTME_X
+};
+
+extern "C" hipError_t svtme_prime_stages(void) { // (see svtme_prime_pyramid): every kernel a job can launch
+    hipFuncAttributes a;
+    for (uint32_t id = 1; id < K_COUNT; id++) {
+        const hipError_t e = hipFuncGetAttributes(&a, (const void *)kStageKernels[id].fn);
+        if (e != hipSuccess)
+            return e;
     }
-    *count = n;
+    return hipSuccess;
 }
 
-// Real-time tune on the split path: the second stage-A round, the HME-L0
-// quadrants of slots 1-7 (areas from slot 0's centre, k_stage_d<true>).
-extern "C" void svtme_stage_a1_list(const svtme_job *job, uint8_t *list, uint32_t *count) {
-    const svtme_controls &c = job->ctrl;
-    uint32_t n = 0;
-    if (svtme_hme_rt(&c) && c.enable_hme_flag && c.enable_hme_level0_flag)
-        for (int s = 1; s < 8; s++) {
-            const int l = s >> 2, r = s & 3;
-            if (l >= job->num_lists || r >= job->num_refs[l])
-                continue;
-            if (!(job->temporal_layer_index > 0 || l == 0))
-                continue;
-            list[n++] = (uint8_t)((TA_L0RT << 3) | s);
-        }
-    *count = n;
-}
-
-// Stage-B refinement list of a job: every (slot, quadrant) HME level 1/2
-// refines (hme_level1_b64 / hme_level2_b64 loop over valid slots with
-// temporal_layer_index > 0 || list 0). Host-side, pure.
-extern "C" void svtme_stage_b_list(const svtme_job *job, uint8_t *list, uint32_t *count) {
-    const svtme_controls &c = job->ctrl;
-    uint32_t n = 0;
-    if (c.enable_hme_flag && (c.enable_hme_level1_flag || c.enable_hme_level2_flag))
-        for (int s = 0; s < 8; s++) {
-            const int l = s >> 2, r = s & 3;
-            if (l >= job->num_lists || r >= job->num_refs[l])
-                continue;
-            if (!(job->temporal_layer_index > 0 || l == 0))
-                continue;
-            for (int q = 0; q < 4; q++) list[n++] = (uint8_t)((s << 2) | q);
-        }
-    *count = n;
-}
-
-// Wide full-pel stage geometry, host-side and pure. The largest search area
-// integer_search_b64 can reach (me_sa max, x mv multiplier, x 3/2 variance
-// growth, rounded up to 8 columns) decides 32-bit argmin keys, and the number
-// of search-row bands per (SB, reference).
-static void fp_area_bound(const svtme_controls *c, uint32_t *w, uint32_t *h) {
-    // min(sa_min x distance, sa_max) (:1303-1304), x mv multiplier (:1305-1310),
-    // rounded up to 8 (:1318), then x 3/2 and rounded again by the variance
-    // growth (:1424-1427) when its threshold can be passed
-    uint32_t mw = c->me_sa.sa_max.width, mh = c->me_sa.sa_max.height;
-    if (c->mv_sa_adj_enabled) {
-        mw *= c->mv_sa_adj_sa_multiplier;
-        mh *= c->mv_sa_adj_sa_multiplier;
-    }
-    mw = (mw + 7) & ~7u;
-    mh = mh < 3 ? 3 : mh;
-    if (c->me_8x8_var_enabled && c->me_sr_mult2_th != 0xFFFFFFFFu) {
-        mw = ((mw * 3 / 2) + 7) & ~7u;
-        mh = mh * 3 / 2;
-    }
-    *w = mw;
-    *h = mh;
-}
-// the same bound for job validation (svtme_host.cpp)
-extern "C" void svtme_fp_area_bound(const svtme_controls *c, uint32_t *w, uint32_t *h) { fp_area_bound(c, w, h); }
-
-// Per-slot search parameters of k_hme that do not depend on the SB: the
-// distance, get_hme_l0_search_area (motion_estimation.c:1800-1867, here with
-// l00 = (0, 0); with the real-time reduction, svtme_hme_rt, k_hme recomputes
-// slots 1-7 per SB) and the pre-HME areas (prehme_core :1580-1587).
-extern "C" void svtme_hme_prepare(DevJob *dj) {
-    const svtme_job &job    = dj->job;
-    const svtme_controls &c = job.ctrl;
-    for (int s = 0; s < 8; s++) {
-        const int l = s >> 2, r = s & 3;
-        const bool valid = l < job.num_lists && r < job.num_refs[l];
-        const uint16_t dist = valid ? svtme::ref_dist_const(job, l, r) : 1;
-        dj->sdist[s] = dist;
-        int16_t w = 0, h = 0;
-        if (valid)
-            svtme::hme_l0_area(c, l, r, dist, 0, 0, &w, &h);
-        dj->l0_sa[s][0] = w;
-        dj->l0_sa[s][1] = h;
-        const uint32_t f = svtme::scaled_dist(dist);
-        for (int k = 0; k < 2; k++) {
-            const uint32_t mw = (uint32_t)c.prehme_sa_cfg[k].sa_min.width * f, xw = c.prehme_sa_cfg[k].sa_max.width;
-            const uint32_t mh = (uint32_t)c.prehme_sa_cfg[k].sa_min.height * f, xh = c.prehme_sa_cfg[k].sa_max.height;
-            dj->ph_sa[s][k][0] = (int16_t)(uint16_t)(mw < xw ? mw : xw);
-            dj->ph_sa[s][k][1] = (int16_t)(uint16_t)(mh < xh ? mh : xh);
-        }
-    }
-}
-
-// k_hme applies: every SB 64 wide, sub-sampled HME rows
-extern "C" bool svtme_hme_fused(const svtme_job *job) {
-    const svtme_controls &c = job->ctrl;
-    return (job->width % 64) == 0 && c.hme_search_method != SVTME_FULL_SAD_SEARCH;
-}
-// the same with the context's path selection (svtme_set_paths) applied
-static bool hme_fused(const DevJob &dj) { return svtme_hme_fused(&dj.job) && !(dj.paths & SVTME_PATH_NO_FUSED_HME); }
-
-// Wavefronts per workgroup of the whole-pass k_hme (one SB each): 3 where ten 3-wave
-// workgroups per CU measured faster than eight 4-wave ones, else 4. A pure function
-// of the job; SVTME_PATH_HME_4WAVES forces 4. Left at 4, not measured at 3: full-SAD
-// full-pel rows, the real-time tune's HME-L0 reduction, more than 4 records.
-extern "C" uint32_t svtme_hme_waves(const svtme_job *job) {
-    const svtme_controls &c = job->ctrl;
-    uint32_t R = 0;
-    for (int l = 0; l < job->num_lists && l < 2; l++) R += job->num_refs[l];
-    return c.me_search_method != SVTME_FULL_SAD_SEARCH && !svtme_hme_rt(&c) && R <= 4 ? 3u : 4u;
-}
-// the same under path selection `paths`
-extern "C" uint32_t svtme_hme_waves_paths(const svtme_job *job, uint32_t paths) {
-    return (paths & SVTME_PATH_HME_4WAVES) ? 4u : svtme_hme_waves(job);
-}
-// and for the launch: 4 wherever the whole-pass k_hme does not run
-static uint32_t hme_waves(const DevJob &dj) {
-    const bool whole = svtme_hme_fused(&dj.job) && dj.parts == 1 &&
-                       !(dj.paths & (SVTME_PATH_NO_FUSED_HME | SVTME_PATH_SPLIT_PASS));
-    return whole ? svtme_hme_waves_paths(&dj.job, dj.paths) : 4u;
-}
-
-// the real-time tune's HME-L0 reduction is on (get_hme_l0_search_area,
-// motion_estimation.c:1811-1819): k_hme<..., RT = true> only
-extern "C" bool svtme_hme_rt(const svtme_controls *c) {
-    return c->enable_me_sr_adjustment && c->distance_based_hme_resizing && c->reduce_hme_l0_sr_th_min &&
-           c->reduce_hme_l0_sr_th_max;
-}
-
-// k_l1_full applies: full-SAD HME rows, HME-L1 without L2, an L1 area of at most
-// 16 x 16 positions (TF-ME levels 0-2)
-extern "C" bool svtme_l1_full(const svtme_controls *c) {
-    return c->hme_search_method == SVTME_FULL_SAD_SEARCH && c->enable_hme_flag && c->enable_hme_level1_flag &&
-           !c->enable_hme_level2_flag && c->hme_l1_sa.width <= 16 && c->hme_l1_sa.height <= 16;
-}
-static bool l1_full(const DevJob &dj) { return svtme_l1_full(&dj.job.ctrl) && !(dj.paths & SVTME_PATH_NO_L1_FULL); }
-
-// k_l0_full applies: full-SAD HME rows, HME-L0 on, no pre-HME, HME-L0 quadrants of
-// at most 16 x 8 positions for every slot, whole source dwords on partial SBs
-extern "C" bool svtme_l0_full(const DevJob *dj) {
-    const svtme_controls &c = dj->job.ctrl;
-    if (c.hme_search_method != SVTME_FULL_SAD_SEARCH || c.prehme_enable || !c.enable_hme_flag ||
-        !c.enable_hme_level0_flag || svtme_hme_rt(&c) || (dj->job.width % 64) % 16 != 0 ||
-        (dj->paths & SVTME_PATH_NO_L0_FULL))
-        return false;
-    for (int s = 0; s < 8; s++)
-        if (dj->l0_sa[s][0] > 16 || dj->l0_sa[s][1] > 16)
-            return false;
-    return true;
-}
-
-// the same test on a job (bench / diagnostics: which kernel runs stage A)
-extern "C" bool svtme_l0_full_job(const svtme_job *job) {
-    DevJob dj{};
-    dj.job = *job;
-    svtme_hme_prepare(&dj);
-    return svtme_l0_full(&dj);
-}
-
-// position rows per lane of k_l0_full: 2 when every quadrant has at most 8 rows
-static bool l0_full_short(const DevJob *dj) {
-    for (int s = 0; s < 8; s++)
-        if (dj->l0_sa[s][1] > 8)
-            return false;
-    return true;
-}
-
-extern "C" bool svtme_fp_k32(const svtme_controls *c) {
-    uint32_t w, h;
-    fp_area_bound(c, &w, &h);
-    return (c->me_8x8_var_enabled ? 1u : 0u) + w * h <= 4096u; // order 0 is the variance probe
-}
-
-// the full-pel area's minimum width reaches 24 positions: 6-quad load sets pay
-extern "C" bool svtme_fp_wide(const svtme_controls *c) {
-    return c->me_sa.sa_min.width >= 24 && c->me_sa.sa_max.width >= 24;
-}
-
-// k_fp_wide applies: sub-sampled rows, 32-bit keys, a wide area of more than one
-// band, and the window of 4 bands in its LDS rows (FPW_PITCH dwords, bands of
-// at most 8 rows with up to 16 parts)
-extern "C" bool svtme_fp_wide_lds(const svtme_controls *c) {
-    if (c->me_search_method == SVTME_FULL_SAD_SEARCH || c->enable_me_sr_adjustment == 2 || !svtme_fp_k32(c) ||
-        !svtme_fp_wide(c))
-        return false;
-    uint32_t w, h;
-    fp_area_bound(c, &w, &h);
-    const uint32_t nsets = ((w + 3) / 4 + FPW_TQ - 1) / FPW_TQ;
-    return (w * h) / 512 >= 2 && 14 + nsets * FPW_TQ + 2 + 1 <= FPW_BOFF && h <= 8 * 16;
-}
-
-static bool fp_wide_lds(const svtme_controls *c, uint32_t paths) {
-    return svtme_fp_wide_lds(c) && !(paths & SVTME_PATH_NO_FP_WIDE);
-}
-static bool fp_wide_lds(const DevJob &dj) { return fp_wide_lds(&dj.job.ctrl, dj.paths); }
-
-// search-row bands per (SB, reference) of the wide full-pel stage under path selection `paths`
-extern "C" uint32_t svtme_fp_parts_paths(const svtme_controls *c, uint32_t paths) {
-    if (c->enable_me_sr_adjustment == 2)
-        return 0; // slot 0's 64x64 SAD feeds the other slots' areas: per-SB k_stage_c
-    uint32_t w, h;
-    fp_area_bound(c, &w, &h);
-    uint32_t parts = (w * h) / 512;
-    if (fp_wide_lds(c, paths)) { // workgroups of 4 bands of <= 8 rows
-        parts = parts > (h + 7) / 8 ? parts : (h + 7) / 8;
-        parts = (parts + 3) & ~3u;
-    }
-    return parts < 1 ? 1 : (parts > 16 ? 16 : parts);
-}
-extern "C" uint32_t svtme_fp_parts(const svtme_controls *c) { return svtme_fp_parts_paths(c, 0); }
-
-// Batch launch key: jobs launched together must agree on it (svtme_host.cpp
-// splits a batch into groups by it).
-extern "C" uint32_t svtme_launch_key(const DevJob *dj) {
-    const bool full = dj->job.ctrl.me_search_method == SVTME_FULL_SAD_SEARCH;
-    return (uint32_t)full | (uint32_t)(dj->parts != 0) << 1 | (uint32_t)svtme_fp_k32(&dj->job.ctrl) << 2 |
-           (uint32_t)(dj->job.ctrl.enable_hme_level2_flag != 0) << 3 | (uint32_t)hme_fused(*dj) << 4 |
-           (uint32_t)(dj->parts == 1) << 5 | (uint32_t)svtme_fp_wide(&dj->job.ctrl) << 6 |
-           (uint32_t)svtme_hme_rt(&dj->job.ctrl) << 7 | (uint32_t)fp_wide_lds(*dj) << 8 |
-           (uint32_t)l1_full(*dj) << 9 | (uint32_t)svtme_l0_full(dj) << 10 |
-           (uint32_t)((dj->paths & SVTME_PATH_SPLIT_PASS) != 0) << 11 | (uint32_t)(hme_waves(*dj) == 3) << 12;
-}
-
-static DevBatch make_batch(const DevJob *d_jobs, const DevJob *h, uint32_t n, uint32_t (*units)(const DevJob &)) {
+static DevBatch make_batch(const DevJob *d_jobs, const DevJob *h, uint32_t n, uint32_t id) {
     DevBatch b;
     b.jobs     = d_jobs;
     b.n        = n;
@@ -4991,7 +4767,7 @@ static DevBatch make_batch(const DevJob *d_jobs, const DevJob *h, uint32_t n, ui
     for (uint32_t k = 0; k < SVTME_MAX_BATCH; k++) {
         b.start[k] = k < n ? t : 0xFFFFFFFFu;
         if (k < n)
-            t += units(h[k]);
+            t += svtme_kernel_units(id, &h[k]);
     }
     b.total = t;
     return b;
@@ -5001,143 +4777,43 @@ static DevBatch make_batch(const DevJob *d_jobs, const DevJob *h, uint32_t n, ui
 // d_jobs: the jobs in device memory; h_jobs: the same jobs on the host (unit
 // counts). ev (optional, timing): ten events, start / stop of stage k in
 // ev[2k], ev[2k+1] (k = A, D, B, C1|C, E), attached to the dispatch packets
-// themselves (hipExtLaunchKernelGGL: no extra packets, no gaps); *mask gets
+// themselves (hipExtLaunchKernel: no extra packets, no gaps); *mask gets
 // bit k for every stage launched. With the real-time tune on the split path,
 // stage A spans both stage-A rounds and the k_stage_d<true> between them.
-#define SVTME_LAUNCH_NT(K, grid, nt, k, ...)                                                                        \
-    do {                                                                                                           \
-        if (ev) {                                                                                                  \
-            hipExtLaunchKernelGGL(K, grid, dim3(nt), 0, s, ev[2 * (k)], ev[2 * (k) + 1], 0, __VA_ARGS__);            \
-            *mask |= 1u << (k);                                                                                    \
-        } else                                                                                                     \
-            hipLaunchKernelGGL(K, grid, dim3(nt), 0, s, __VA_ARGS__);                                              \
-    } while (0)
-#define SVTME_LAUNCH(K, grid, k, ...) SVTME_LAUNCH_NT(K, grid, 256, k, __VA_ARGS__)
-
-extern "C" hipError_t svtme_prime_stages(void) { // (see svtme_prime_pyramid): every kernel a job can launch
-    const void *k[] = {
-        (const void *)svtme::k_hme<true, true, true, false>,   (const void *)svtme::k_hme<true, true, true, true>,
-        (const void *)svtme::k_hme<false, true, true, false>,  (const void *)svtme::k_hme<true, true, false, false>,
-        (const void *)svtme::k_hme<true, true, true, false, 3>, (const void *)svtme::k_hme<true, true, false, false, 3>,
-        (const void *)svtme::k_stage_a<false>,                 (const void *)svtme::k_stage_a<true>,
-        (const void *)svtme::k_stage_d<false>,                 (const void *)svtme::k_stage_d<true>,
-        (const void *)svtme::k_stage_b<false>,                 (const void *)svtme::k_stage_b<true>,
-        (const void *)svtme::k_stage_c<false>,                 (const void *)svtme::k_stage_c<true>,
-        (const void *)svtme::k_stage_c1<true, true, true>,     (const void *)svtme::k_stage_c1<true, true>,
-        (const void *)svtme::k_stage_c1<true, false>,          (const void *)svtme::k_stage_c1<false, true, true>,
-        (const void *)svtme::k_stage_c1<false, true>,          (const void *)svtme::k_stage_c1<false, false>,
-        (const void *)svtme::k_l0_full<2>,                     (const void *)svtme::k_l0_full<4>,
-        (const void *)svtme::k_l1_full,                        (const void *)svtme::k_fp_wide,
-        (const void *)svtme::k_stage_e};
-    hipFuncAttributes a;
-    for (const void *f : k) {
-        const hipError_t e = hipFuncGetAttributes(&a, f);
-        if (e != hipSuccess)
-            return e;
-    }
-    return hipSuccess;
-}
-
 extern "C" hipError_t svtme_launch_stages(const DevJob *d_jobs, const DevJob *h_jobs, uint32_t n, hipStream_t s,
                                           hipEvent_t *ev, uint32_t *mask) {
     if (n == 0 || n > SVTME_MAX_BATCH)
         return hipErrorInvalidValue;
-    const DevJob &h0 = h_jobs[0];
     if (mask)
         *mask = 0;
-    const DevBatch bd = make_batch(d_jobs, h_jobs, n, [](const DevJob &j) { return j.job.sb_count; });
-    const bool full = h0.job.ctrl.me_search_method == SVTME_FULL_SAD_SEARCH;
-    const bool k32  = svtme_fp_k32(&h0.job.ctrl);
-    // the whole pass in one launch; SVTME_PATH_SPLIT_PASS keeps k_hme -> k_stage_c1 -> k_stage_e (diagnostics)
-    const bool rt = svtme_hme_rt(&h0.job.ctrl); // the real-time tune's HME-L0 reduction
-#define SVTME_HME(FP, SUB, K32)                                                                                     \
-    do {                                                                                                           \
-        if (rt)                                                                                                    \
-            SVTME_LAUNCH((svtme::k_hme<FP, SUB, K32, true>), dim3(bd.total), 0, bd);                               \
-        else                                                                                                       \
-            SVTME_LAUNCH((svtme::k_hme<FP, SUB, K32, false>), dim3(bd.total), 0, bd);                              \
-    } while (0)
-    if (hme_fused(h0) && h0.parts == 1 && !(h0.paths & SVTME_PATH_SPLIT_PASS)) {
-        if (hme_waves(h0) == 3 && k32) // (svtme_hme_waves: sub-sampled rows, no real-time reduction)
-            SVTME_LAUNCH_NT((svtme::k_hme<true, true, true, false, 3>), dim3(bd.total), 192, 0, bd);
-        else if (hme_waves(h0) == 3)
-            SVTME_LAUNCH_NT((svtme::k_hme<true, true, false, false, 3>), dim3(bd.total), 192, 0, bd);
-        else if (full && k32)
-            SVTME_HME(true, false, true);
-        else if (full)
-            SVTME_HME(true, false, false);
-        else if (k32)
-            SVTME_HME(true, true, true);
+    LaunchPlan p;
+    svtme_launch_plan_group(h_jobs, n, &p);
+    // kernel `id` over the jobs' units of it, with events on its dispatch packet (ext); false: no units.
+    // A failed launch shows in hipGetLastError below.
+    auto launch = [&](uint32_t id, bool ext, hipEvent_t start, hipEvent_t stop) {
+        const StageKernel &k = kStageKernels[id];
+        DevBatch b           = make_batch(d_jobs, h_jobs, n, id);
+        if (!b.total)
+            return false;
+        const dim3 grid((b.total + k.per_wg - 1) / k.per_wg), block(k.threads);
+        void *args[] = {&b};
+        if (ext)
+            (void)hipExtLaunchKernel((const void *)k.fn, grid, block, args, 0, s, start, stop, 0);
         else
-            SVTME_HME(true, true, false);
-        return hipGetLastError();
+            (void)hipLaunchKernel((const void *)k.fn, grid, block, args, 0, s);
+        return true;
+    };
+    for (int k = 0; k < SLOT_COUNT; k++) {
+        if (p.kernel[k] && launch(p.kernel[k], ev != nullptr, ev ? ev[2 * k] : nullptr, ev ? ev[2 * k + 1] : nullptr) && ev)
+            *mask |= 1u << k;
+        if (k == SLOT_A && p.rt_round) { // the real-time tune: slot 0's HME-L0 centre, then the other slots' HME-L0
+            // timed as part of stage 0: the last of these launches re-records stage 0's stop event
+            const bool r1 = make_batch(d_jobs, h_jobs, n, K_STAGE_A_R1).total != 0;
+            launch(K_STAGE_D_RT0, true, nullptr, ev && !r1 ? ev[1] : nullptr);
+            launch(K_STAGE_A_R1, true, nullptr, ev ? ev[1] : nullptr);
+            if (ev)
+                *mask |= 1u;
+        }
     }
-    if (hme_fused(h0)) {
-        SVTME_HME(false, true, true);
-    } else {
-    const DevBatch ba = make_batch(d_jobs, h_jobs, n, [](const DevJob &j) { return j.job.sb_count * j.ta_count; });
-    bool short_l0 = true;
-    for (uint32_t k = 0; k < n; k++)
-        short_l0 = short_l0 && l0_full_short(&h_jobs[k]);
-    if (ba.total && svtme_l0_full(&h0) && short_l0)
-        SVTME_LAUNCH(svtme::k_l0_full<2>, dim3((ba.total + 3) / 4), 0, ba);
-    else if (ba.total && svtme_l0_full(&h0))
-        SVTME_LAUNCH(svtme::k_l0_full<4>, dim3((ba.total + 3) / 4), 0, ba);
-    else if (ba.total)
-        SVTME_LAUNCH(svtme::k_stage_a<false>, dim3((ba.total + 3) / 4), 0, ba);
-    if (rt) { // the real-time tune: slot 0's HME-L0 centre, then the other slots' HME-L0
-        const DevBatch ba1 =
-            make_batch(d_jobs, h_jobs, n, [](const DevJob &j) { return j.job.sb_count * j.ta1_count; });
-        // timed as part of stage 0: the last of these launches re-records stage 0's stop event
-        hipEvent_t stop_d = ev && !ba1.total ? ev[1] : nullptr, stop_a = ev ? ev[1] : nullptr;
-        hipExtLaunchKernelGGL(svtme::k_stage_d<true>, dim3((bd.total + 3) / 4), dim3(256), 0, s, nullptr, stop_d, 0, bd);
-        if (ba1.total)
-            hipExtLaunchKernelGGL(svtme::k_stage_a<true>, dim3((ba1.total + 3) / 4), dim3(256), 0, s, nullptr, stop_a, 0,
-                                  ba1);
-        if (ev)
-            *mask |= 1u;
-    }
-    SVTME_LAUNCH(svtme::k_stage_d<false>, dim3((bd.total + 3) / 4), 1, bd);
-    const DevBatch bb = make_batch(d_jobs, h_jobs, n, [](const DevJob &j) { return j.job.sb_count * j.tb_count; });
-    if (bb.total && l1_full(h0)) { // two quadrants per wavefront
-        const DevBatch b2 =
-            make_batch(d_jobs, h_jobs, n, [](const DevJob &j) { return j.job.sb_count * (j.tb_count / 2); });
-        SVTME_LAUNCH(svtme::k_l1_full, dim3((b2.total + 3) / 4), 2, b2);
-    } else if (bb.total) {
-        if (h0.job.ctrl.enable_hme_level2_flag)
-            SVTME_LAUNCH(svtme::k_stage_b<true>, dim3((bb.total + 3) / 4), 2, bb);
-        else
-            SVTME_LAUNCH(svtme::k_stage_b<false>, dim3((bb.total + 3) / 4), 2, bb);
-    }
-    }
-    const DevBatch be = make_batch(d_jobs, h_jobs, n, [](const DevJob &j) { return j.job.sb_count; });
-    if (h0.parts) { // wide full-pel stage + per-SB decode
-        const DevBatch bc = make_batch(d_jobs, h_jobs, n, [](const DevJob &j) { return j.job.sb_count * j.R * j.parts; });
-        const dim3 grid((bc.total + 3) / 4);
-        const bool wide = svtme_fp_wide(&h0.job.ctrl);
-        if (fp_wide_lds(h0))
-            SVTME_LAUNCH(svtme::k_fp_wide, grid, 3, bc);
-        else if (full && k32 && wide)
-            SVTME_LAUNCH((svtme::k_stage_c1<false, true, true>), grid, 3, bc);
-        else if (full && k32)
-            SVTME_LAUNCH((svtme::k_stage_c1<false, true>), grid, 3, bc);
-        else if (full)
-            SVTME_LAUNCH((svtme::k_stage_c1<false, false>), grid, 3, bc);
-        else if (k32 && wide)
-            SVTME_LAUNCH((svtme::k_stage_c1<true, true, true>), grid, 3, bc);
-        else if (k32)
-            SVTME_LAUNCH((svtme::k_stage_c1<true, true>), grid, 3, bc);
-        else
-            SVTME_LAUNCH((svtme::k_stage_c1<true, false>), grid, 3, bc);
-        bool direct = true; // every record made by k_stage_c1 (direct_records)
-        for (uint32_t k = 0; k < n; k++)
-            direct = direct && h_jobs[k].job.me_type == SVTME_ME_MCTF && h_jobs[k].parts == 1 && !h_jobs[k].out_sb &&
-                     !fp_wide_lds(h_jobs[k]);
-        if (!direct)
-            SVTME_LAUNCH(svtme::k_stage_e, dim3(be.total), 4, be);
-    } else if (full)
-        SVTME_LAUNCH(svtme::k_stage_c<false>, dim3(be.total), 3, be);
-    else
-        SVTME_LAUNCH(svtme::k_stage_c<true>, dim3(be.total), 3, be);
     return hipGetLastError();
 }

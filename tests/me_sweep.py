@@ -416,6 +416,22 @@ def lib_of(S):
     return lib
 
 
+def plan_lib_of(S):
+    """lib_of, with the functions the launch-plan helpers below call."""
+    lib = lib_of(S)
+    lib.svtme_fp_parts_paths.argtypes = [C.POINTER(S.Controls), C.c_uint32]
+    lib.svtme_fp_parts_paths.restype = C.c_uint32
+    for f in ("svtme_stage_a_list", "svtme_stage_a1_list", "svtme_stage_b_list"):
+        getattr(lib, f).argtypes = [C.POINTER(S.Job), C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)]
+        getattr(lib, f).restype = None
+    lib.svtme_job_kernels.argtypes = [C.POINTER(S.Job), C.c_uint32, C.c_int, C.POINTER(C.c_uint8),
+                                      C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)]
+    lib.svtme_job_kernels.restype = C.c_uint32
+    lib.svtme_kernel_name.argtypes = [C.c_uint32]
+    lib.svtme_kernel_name.restype = C.c_char_p
+    return lib
+
+
 def dispatch_of(S, lib, job) -> dict:
     c = C.byref(job.ctrl)
     return {"fused": bool(lib.svtme_hme_fused(C.byref(job))), "waves": int(lib.svtme_hme_waves(C.byref(job))),
@@ -455,3 +471,123 @@ def launch_class(d: dict) -> tuple:
     return (d["full_me"], d["parts"] != 0, d["k32"], d["l2"], d["fused"], d["parts"] == 1, d["fp_wide"], d["rt"],
             d["fp_wide_lds"], d["l1_full"] and not d["fused"], d["l0_full"] and not d["fused"],
             whole and d["waves"] == 3)
+
+
+# ----------------------------------------------------------------------------
+# the launch plan: what the library reports, and the same decision restated from the predicates
+# ----------------------------------------------------------------------------
+SLOTS = ["A", "D", "B", "C", "E"]  # the timing slots of GpuME.timing_read
+
+
+def kernel_names(lib) -> list:
+    """Name by kernel id; ids start at 1 and end before the first id without a name."""
+    names = [None]
+    while lib.svtme_kernel_name(len(names)) is not None:
+        names.append(lib.svtme_kernel_name(len(names)).decode())
+    return names
+
+
+def plan_of(lib, job, paths: int = 0, with_sb: bool = True):
+    """The library's answer for a job submitted alone -> ([(slot, kernel name)] in launch order, launch key)."""
+    ids, slots, key = (C.c_uint8 * 8)(), (C.c_uint8 * 8)(), C.c_uint32()
+    n = lib.svtme_job_kernels(C.byref(job), paths, int(with_sb), ids, slots, C.byref(key))
+    return [(SLOTS[slots[k]], lib.svtme_kernel_name(ids[k]).decode()) for k in range(n)], key.value
+
+
+def _l0_short(job) -> bool:
+    """Every slot's HME-L0 quadrant has at most 8 rows: the height of get_hme_l0_search_area
+    (svtme_device.h, hme_l0_area) with l00 = (0, 0), as svtme_hme_prepare takes it."""
+    c = job.ctrl
+    for l in range(job.num_lists):
+        for r in range(job.num_refs[l]):
+            dist = abs(job.picture_number - job.ref_picture_number[l][r]) & 0xFFFF
+            mn, mx = c.hme_l0_sa.sa_min.height, c.hme_l0_sa.sa_max.height
+            if c.enable_me_sr_adjustment and c.distance_based_hme_resizing:
+                is_ver, is_still = True, False
+                if c.reduce_hme_l0_sr_th_min and c.reduce_hme_l0_sr_th_max and (l or r):
+                    is_ver, is_still = False, True  # |mv| = 0: below 3 * th_min, not above th_max
+                yo = 4 if c.enable_me_sr_adjustment == 2 and is_still else 1 if is_ver else 2
+                mn, mx = mn // (yo + r), mx // (yo + r)
+            f = dist * 5 // 8 + (1 if dist % 8 else 0)
+            if min(mn // c.num_hme_sa_h * f, mx // c.num_hme_sa_h) > 8:
+                return False
+    return True
+
+
+def kernels_of(S, lib, job, paths: int = 0, with_sb: bool = True) -> list:
+    """[(slot, kernel name)] of a job submitted alone, in launch order: the launcher's decision as it
+    stood when it evaluated the predicates itself, restated from the exported predicates."""
+    d = dispatch_of(S, lib, job)
+    c = job.ctrl
+    count = {}
+    for f in ("a", "a1", "b"):
+        buf, n = (C.c_uint8 * 64)(), C.c_uint32()
+        getattr(lib, f"svtme_stage_{f}_list")(C.byref(job), buf, C.byref(n))
+        count[f] = n.value
+    b = lambda v: "true" if v else "false"  # noqa: E731
+    full, k32, rt = d["full_me"], d["k32"], d["rt"]
+    fused = d["fused"] and not paths & S.PATH_NO_FUSED_HME
+    parts = lib.svtme_fp_parts_paths(C.byref(c), paths)
+    wide_lds = d["fp_wide_lds"] and not paths & S.PATH_NO_FP_WIDE
+    if fused and parts == 1 and not paths & S.PATH_SPLIT_PASS:
+        waves = 4 if paths & S.PATH_HME_4WAVES else d["waves"]
+        if waves == 3:
+            return [("A", f"k_hme<true, true, {b(k32)}, false, 3>")]
+        return [("A", f"k_hme<true, {b(not full)}, {b(k32)}, {b(rt)}>")]
+    out = []
+    if fused:
+        out.append(("A", f"k_hme<false, true, true, {b(rt)}>"))
+    else:
+        if count["a"] and d["l0_full"] and not paths & S.PATH_NO_L0_FULL:
+            out.append(("A", "k_l0_full<2>" if _l0_short(job) else "k_l0_full<4>"))
+        elif count["a"]:
+            out.append(("A", "k_stage_a<false>"))
+        if rt:
+            out.append(("A", "k_stage_d<true>"))
+            if count["a1"]:
+                out.append(("A", "k_stage_a<true>"))
+        out.append(("D", "k_stage_d<false>"))
+        if count["b"] and d["l1_full"] and not paths & S.PATH_NO_L1_FULL:
+            out.append(("B", "k_l1_full"))
+        elif count["b"]:
+            out.append(("B", f"k_stage_b<{b(d['l2'])}>"))
+    if parts:
+        if wide_lds:
+            out.append(("C", "k_fp_wide"))
+        elif k32 and d["fp_wide"]:
+            out.append(("C", f"k_stage_c1<{b(not full)}, true, true>"))
+        else:
+            out.append(("C", f"k_stage_c1<{b(not full)}, {b(k32)}>"))
+        if not (job.me_type == S.ME_MCTF and parts == 1 and not with_sb and not wide_lds):
+            out.append(("E", "k_stage_e"))
+    else:
+        out.append(("C", f"k_stage_c<{b(not full)}>"))
+    return out
+
+
+def launch_key_before(S, lib, job, paths: int = 0) -> tuple:
+    """The thirteen facts svtme_launch_key packed before it became a packing of the launch plan,
+    under path bits `paths` (launch_class is the same at paths 0)."""
+    d = dispatch_of(S, lib, job)
+    parts = lib.svtme_fp_parts_paths(C.byref(job.ctrl), paths)
+    fused = d["fused"] and not paths & S.PATH_NO_FUSED_HME
+    whole = fused and parts == 1 and not paths & S.PATH_SPLIT_PASS
+    waves = 4 if paths & S.PATH_HME_4WAVES else d["waves"]
+    return (d["full_me"], parts != 0, d["k32"], d["l2"], fused, parts == 1, d["fp_wide"], d["rt"],
+            d["fp_wide_lds"] and not paths & S.PATH_NO_FP_WIDE, d["l1_full"] and not paths & S.PATH_NO_L1_FULL,
+            d["l0_full"] and not paths & S.PATH_NO_L0_FULL, bool(paths & S.PATH_SPLIT_PASS), whole and waves == 3)
+
+
+def _role(slot: str, name: str) -> tuple:
+    """What a kernel does in its launch: its slot and, in slot A, its place in the real-time round;
+    k_l0_full's rows per lane are one of the two facts a launch reduces over its jobs."""
+    return (slot, {"k_stage_d<true>": 1, "k_stage_a<true>": 2}.get(name, 0))
+
+
+def one_launch(a: list, b: list) -> bool:
+    """Two jobs' kernel lists can be one launch: wherever both run a kernel in the same role it is the
+    same kernel. A job leaves a role out when it has no work units for it (no HME levels 1 / 2: no
+    slot B) or when a reducible fact says so (every record direct: no k_stage_e)."""
+    ra = {_role(s, n): "k_l0_full" if n.startswith("k_l0_full") else n for s, n in a}
+    rb = {_role(s, n): "k_l0_full" if n.startswith("k_l0_full") else n for s, n in b}
+    return all(ra[r] == rb[r] for r in ra.keys() & rb.keys())
