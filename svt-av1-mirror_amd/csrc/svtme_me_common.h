@@ -96,6 +96,11 @@ __device__ __forceinline__ int wave_incl_scan(int v) {
 // exact n / d for n * d < 2^32 with m = magic_u32(d); d == 1 wraps m to 0
 __device__ __forceinline__ uint32_t magic_u32(uint32_t d) { return 0xFFFFFFFFu / d + 1u; }
 __device__ __forceinline__ int mdiv(int n, uint32_t m) { return m ? (int)__umulhi((uint32_t)n, m) : n; }
+// exact n / d for 0 <= n < 2^20 and d > 0 with r = rdiv_of(d), in full-rate float ops and with no
+// integer division to make r: (n + 0.5) / d lies at least 0.5 / d from an integer, and v_rcp_f32
+// (1 ulp) and the product's rounding move it by less than (n + 0.5) / d * 2^-21.6
+__device__ __forceinline__ float rdiv_of(int d) { return __builtin_amdgcn_rcpf((float)d); }
+__device__ __forceinline__ int rdiv(int n, float r) { return (int)(((float)n + 0.5f) * r); }
 
 // XCD-aware block order: blocks b and b + 8 share an XCD (round-robin
 // dispatch), so each XCD gets one contiguous band of work whose reference

@@ -1127,6 +1127,12 @@ __device__ __forceinline__ unsigned long long qsad64(unsigned long long ref, uin
 __device__ __forceinline__ unsigned long long pair(uint32_t lo, uint32_t hi) {
     return ((unsigned long long)hi << 32) | lo;
 }
+// (high dword of a, low dword of b) in one VALU op
+__device__ __forceinline__ unsigned long long pair_hi_lo(unsigned long long a, unsigned long long b) {
+    unsigned long long r;
+    asm("v_pk_mov_b32 %0, %1, %2 op_sel:[1,0]" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
 
 struct HSrch {             // one 1/16-resolution search (pre-HME region or HME-L0 quadrant)
     const uint8_t *a0;     // dword-aligned plane address of window dword 0, position row 0
@@ -1134,7 +1140,7 @@ struct HSrch {             // one 1/16-resolution search (pre-HME region or HME-
     int16_t sa_w, ncols;   // positions per row; tile columns
     int16_t cnt0, cnt1;    // position rows of each tile-row parity (skip: cnt0 = rows, cnt1 = 0)
     int16_t ylast;         // last plane-row offset a tile of this search may read
-    uint32_t ncm;          // magic_u32(ncols): tile index / ncols by multiply-high
+    float ncr;             // rdiv_of(ncols): tile index / ncols (rdiv)
     uint8_t sh, skip, id;  // byte offset of position 0; odd rows only; ARes index
     uint8_t need;          // bit of HmeSh::need (slot * 2 + (L0 ? 1 : 0))
     uint8_t tt;            // position rows per tile: HT16, or 2 (the HME-L0 group, see k_hme A1)
@@ -1142,7 +1148,7 @@ struct HSrch {             // one 1/16-resolution search (pre-HME region or HME-
 struct HSrch1 {            // one HME-L1 refinement search
     const uint8_t *a0;
     int32_t item0;
-    uint32_t ncm;          // magic_u32(ncols)
+    float ncr;             // rdiv_of(ncols)
     int16_t sa_w, ncols;
     uint8_t sh, id;        // id = slot * 4 + quadrant
 };
@@ -1187,9 +1193,12 @@ __device__ __forceinline__ unsigned long long hme_tile16(const uint8_t *a0, int 
         const Row8 &R = buf[m % 3];
         static_assert(HQ16 + 4 == 6, "Row8 holds 6 dwords");
         const uint32_t d[6] = {R.lo.x, R.lo.y, R.lo.z, R.lo.w, R.hi.x, R.hi.y};
+        // the 5 dword pairs the qsads read: the odd ones from their neighbours, one v_pk_mov_b32 each
         unsigned long long P[HQ16 + 3];
 #pragma unroll
-        for (int j = 0; j < HQ16 + 3; j++) P[j] = pair(d[j], d[j + 1]);
+        for (int j = 0; j < HQ16 + 3; j += 2) P[j] = pair(d[j], d[j + 1]);
+#pragma unroll
+        for (int j = 1; j < HQ16 + 3; j += 2) P[j] = pair_hi_lo(P[j - 1], P[j + 1]);
 #pragma unroll
         for (int t = 0; t < T; t++) {
             const int k = m - t;
@@ -1203,34 +1212,51 @@ __device__ __forceinline__ unsigned long long hme_tile16(const uint8_t *a0, int 
                 for (int j = 0; j < 4; j++) acc[t][qq] = qsad64(P[qq + j], sr[k][j], acc[t][qq]);
         }
     }
-    uint32_t xo[HQ16][4];
-#pragma unroll
-    for (int qq = 0; qq < HQ16; qq++)
-#pragma unroll
-        for (int e = 0; e < 4; e++) {
-            const int x = 4 * (q0 + qq) - sh + e;
-            xo[qq][e]   = (x >= 0 && x < sa_w) ? (uint32_t)x : U32MAX;
-        }
+    // a wavefront whose tiles all lie inside their areas (interior windows: dword aligned,
+    // 8 k wide) tests no position: a key is sad << 16 | e, e = 0 .. 7, and the tile's first x
+    // is added to the minimum key (the same term in its 8 keys: their order stands)
+    const int x0 = 4 * q0 - sh;
+    const bool inner = __builtin_amdgcn_ballot_w64(x0 < 0 || x0 + 4 * HQ16 > sa_w) == 0;
     unsigned long long best = ~0ull;
     // the key rows from a fresh copy of yf: CSE with the row addresses above keeps
     // yf + 2t live through the loop (a spill at 64 VGPRs)
     uint32_t yk = (uint32_t)yf;
     asm volatile("" : "+v"(yk));
+    auto rows = [&](auto in, const uint32_t (&xo)[HQ16][4]) {
+        constexpr bool IN = decltype(in)::value;
 #pragma unroll
-    for (int t = 0; t < T; t++) {
-        uint32_t mt = U32MAX;
+        for (int t = 0; t < T; t++) {
+            uint32_t mt = U32MAX;
 #pragma unroll
-        for (int qq = 0; qq < HQ16; qq++) {
-            const uint32_t lo = (uint32_t)acc[t][qq], hi = (uint32_t)(acc[t][qq] >> 32);
-            const uint32_t k0 = (lo << 16) | xo[qq][0], k1 = (lo & 0xFFFF0000u) | xo[qq][1];
-            const uint32_t k2 = (hi << 16) | xo[qq][2], k3 = (hi & 0xFFFF0000u) | xo[qq][3];
-            mt = min_u32(mt, min_u32(min_u32(k0, k1), min_u32(k2, k3)));
+            for (int qq = 0; qq < HQ16; qq++) {
+                const uint32_t lo = (uint32_t)acc[t][qq], hi = (uint32_t)(acc[t][qq] >> 32);
+                const uint32_t k0 = (lo << 16) | xo[qq][0], k1 = (lo & 0xFFFF0000u) | xo[qq][1];
+                const uint32_t k2 = (hi << 16) | xo[qq][2], k3 = (hi & 0xFFFF0000u) | xo[qq][3];
+                mt = min_u32(mt, min_u32(min_u32(k0, k1), min_u32(k2, k3)));
+            }
+            if (IN)
+                mt += (uint32_t)x0; // (x0 + 7 < sa_w < 2^16: no carry into the SAD; SADs are below 2^15)
+            if (t < tv && (IN || mt != U32MAX)) {
+                const unsigned long long kk = ((unsigned long long)(mt >> 16) << 32) |
+                                              ((unsigned long long)(yk + 2 * t) << 16) | (mt & 0xFFFFu);
+                best = kk < best ? kk : best;
+            }
         }
-        if (t < tv && mt != U32MAX) {
-            const unsigned long long kk = ((unsigned long long)(mt >> 16) << 32) |
-                                          ((unsigned long long)(yk + 2 * t) << 16) | (mt & 0xFFFFu);
-            best = kk < best ? kk : best;
-        }
+    };
+    if (inner) {
+        static_assert(HQ16 == 2, "a tile's 8 positions");
+        const uint32_t xe[HQ16][4] = {{0, 1, 2, 3}, {4, 5, 6, 7}};
+        rows(std::true_type(), xe);
+    } else {
+        uint32_t xo[HQ16][4];
+#pragma unroll
+        for (int qq = 0; qq < HQ16; qq++)
+#pragma unroll
+            for (int e = 0; e < 4; e++) {
+                const int x = x0 + 4 * qq + e;
+                xo[qq][e]   = (x >= 0 && x < sa_w) ? (uint32_t)x : U32MAX;
+            }
+        rows(std::false_type(), xo);
     }
     return best;
 }
@@ -1253,22 +1279,23 @@ __device__ __forceinline__ unsigned long long hme_tile32q(const uint8_t *a0, int
         u32x4a4 a, b;
         u32x3a4 c;
     };
+    // block row 4g + kk (< 16) is plane row y + 2 (4g + kk): the lane's first row, then steps
+    // of two plane rows (a uniform stride: one 64-bit add each)
+    const int st2      = 2 * UNI(stride);
+    const uint8_t *rp0 = a0 + (ptrdiff_t)(y + 8 * g) * stride + 4 * q0;
     auto ld = [&](int kk, Row11 &L) {
-        const int k        = min(4 * g + kk, 15);
-        const uint32_t *rp = (const uint32_t *)(a0 + (ptrdiff_t)(y + 2 * k) * stride) + q0;
+        const uint32_t *rp = (const uint32_t *)(rp0 + (ptrdiff_t)(kk * st2));
         L.a = ldg4(rp), L.b = ldg4(rp + 4), L.c = *(gu3 *)(uintptr_t)(rp + 8);
     };
     Row11 L[2];
     ld(0, L[0]);
+    const bool fullh = UNI(kh1) == 16; // wave-uniform: no row of the block is dropped
     unsigned long long acc[HQ1] = {};
 #pragma unroll
     for (int kk = 0; kk < 4; kk++) {
         if (kk + 1 < 4)
             ld(kk + 1, L[(kk + 1) & 1]);
-        // every row is summed and rows past the block height (a partial SB, a
-        // per-lane test) are dropped by a select: no divergent branch, whose
-        // join would wait for the row prefetched above
-        const int k = min(4 * g + kk, 15);
+        const int k = 4 * g + kk;
         {
             const Row11 &R = L[kk & 1];
             const uint4 s0 = ((const uint4 *)src[k])[0], s1 = ((const uint4 *)src[k])[1];
@@ -1276,28 +1303,69 @@ __device__ __forceinline__ unsigned long long hme_tile32q(const uint8_t *a0, int
             uint32_t d[11] = {R.a.x, R.a.y, R.a.z, R.a.w, R.b.x, R.b.y, R.b.z, R.b.w, R.c.x, R.c.y, R.c.z};
 #pragma unroll
             for (int j = 0; j < HQ1 + 8; j++) d[j] = __builtin_amdgcn_alignbyte(d[j + 1], d[j], (uint32_t)sh);
-            const bool use = FULLK || 4 * g + kk < kh1;
+            // the dword pairs (d[j], d[j + 1]) the qsads read, in even-aligned registers: the
+            // even ones as realigned, each odd one from its two neighbours in one v_pk_mov_b32
+            // (left to the compiler, every pair but the first costs a v_mov_b32)
+            static_assert(HQ1 + 8 == 10, "pairs 0 .. 8 of 10 realigned dwords");
+            unsigned long long P[HQ1 + 7];
+#pragma unroll
+            for (int j = 0; j < HQ1 + 7; j += 2) P[j] = pair(d[j], d[j + 1]);
+#pragma unroll
+            for (int j = 1; j < HQ1 + 7; j += 2) P[j] = pair_hi_lo(P[j - 1], P[j + 1]);
+            unsigned long long a[HQ1];
 #pragma unroll
             for (int qq = 0; qq < HQ1; qq++) {
-                unsigned long long a = acc[qq];
+                a[qq] = acc[qq];
 #pragma unroll
-                for (int j = 0; j < 8; j++) a = qsad64(pair(d[qq + j], d[qq + j + 1]), sv[j], a);
-                acc[qq] = use ? a : acc[qq];
+                for (int j = 0; j < 8; j++) a[qq] = qsad64(P[qq + j], sv[j], a[qq]);
             }
+            // rows past the block height (a partial SB, a per-lane test) are summed and then
+            // dropped by a select: no divergent branch, whose join would wait for the row
+            // prefetched above. The selects sit behind a scalar branch: a full-height SB
+            // (kh1 == 16) runs none
+            if (!FULLK && !fullh) {
+                const bool use = k < kh1;
+#pragma unroll
+                for (int qq = 0; qq < HQ1; qq++) {
+                    uint32_t lo = use ? (uint32_t)a[qq] : (uint32_t)acc[qq];
+                    uint32_t hi = use ? (uint32_t)(a[qq] >> 32) : (uint32_t)(acc[qq] >> 32);
+                    asm volatile("" : "+v"(lo), "+v"(hi)); // (not if-converted back into unconditional selects)
+                    a[qq] = pair(lo, hi);
+                }
+            }
+#pragma unroll
+            for (int qq = 0; qq < HQ1; qq++) acc[qq] = a[qq];
         }
     }
-    uint32_t mt = U32MAX; // sad (< 2^17) << 15 | x (< 2^15)
+    // the quad's 4 row groups: lanes g ^ 1 summed as packed halves (a lane's SADs are at most
+    // 4 rows x 32 x 255 = 32 640, two lanes' fit 16 bits), then lanes g ^ 2 per position
+    uint32_t v[HQ1][4];
 #pragma unroll
     for (int qq = 0; qq < HQ1; qq++) {
-        uint32_t a[4] = {0, 0, 0, 0};
-        qsad_unpack(acc[qq], a);
+        const uint32_t lo = dpp_add<0xB1>((uint32_t)acc[qq]), hi = dpp_add<0xB1>((uint32_t)(acc[qq] >> 32));
+        v[qq][0] = dpp_add<0x4E>(lo & 0xFFFFu), v[qq][1] = dpp_add<0x4E>(lo >> 16);
+        v[qq][2] = dpp_add<0x4E>(hi & 0xFFFFu), v[qq][3] = dpp_add<0x4E>(hi >> 16);
+    }
+    uint32_t mt = U32MAX; // sad (< 2^17) << 15 | x (< 2^15)
+    static_assert(HQ1 == 2, "a tile's 8 positions: x = 8 * column + 0 .. 7");
+    if (__builtin_amdgcn_ballot_w64(4 * (q0 + HQ1) > sa_w) == 0) {
+        // every tile of the wavefront lies inside its area (areas 8 wide and more are
+        // multiples of 8): no position test, and the tile's first x (a multiple of 8, the
+        // same in its 8 keys) joins the minimum key, not each key
 #pragma unroll
-        for (int e = 0; e < 4; e++) {
-            const uint32_t v = dpp_add<0x4E>(dpp_add<0xB1>(a[e])); // the quad's 4 row groups
-            const int x      = 4 * (q0 + qq) + e;
-            if (x < sa_w)
-                mt = min_u32(mt, (v << 15) | (uint32_t)x);
-        }
+        for (int qq = 0; qq < HQ1; qq++)
+#pragma unroll
+            for (int e = 0; e < 4; e++) mt = min_u32(mt, (v[qq][e] << 15) | (uint32_t)(4 * qq + e));
+        mt |= (uint32_t)(4 * q0);
+    } else {
+#pragma unroll
+        for (int qq = 0; qq < HQ1; qq++)
+#pragma unroll
+            for (int e = 0; e < 4; e++) {
+                const int x = 4 * (q0 + qq) + e;
+                if (x < sa_w)
+                    mt = min_u32(mt, (v[qq][e] << 15) | (uint32_t)x);
+            }
     }
     if (mt == U32MAX)
         return ~0ull;
@@ -3970,7 +4038,7 @@ __device__ __forceinline__ void a1_table(HmeA &A, const DevJob &dj, uint32_t vma
             e.skip            = skip;
             const int nq      = (e.sh + sw + 3) >> 2;
             e.ncols           = (int16_t)((nq + HQ16 - 1) / HQ16);
-            e.ncm             = magic_u32((uint32_t)e.ncols);
+            e.ncr             = rdiv_of(e.ncols);
             if (skip) {
                 e.cnt0  = (int16_t)nrows;
                 e.cnt1  = 0;
@@ -4275,7 +4343,7 @@ __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(HM
                 if (gated && a1_mirrored(sh.u.a, c, need, e.id))
                     continue; // phase D mirrors list 0's result (check_prehme_early_exit)
                 const int local = it - e.item0;
-                const int rt = mdiv(local, e.ncm), col = local - rt * e.ncols;
+                const int rt = rdiv(local, e.ncr), col = local - rt * e.ncols;
                 // the wavefront's tiles all have e.tt rows (the groups are 64-aligned)
                 auto run = [&](auto TT) {
                     constexpr int T = decltype(TT)::value;
@@ -4522,7 +4590,7 @@ __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(HM
                         e.a0              = w0 - e.sh;
                         e.sa_w            = sw;
                         e.ncols           = (int16_t)((((sw + 3) >> 2) + HQ1 - 1) / HQ1); // realigned rows
-                        e.ncm             = magic_u32((uint32_t)e.ncols);
+                        e.ncr             = rdiv_of(e.ncols);
                         e.id              = (uint8_t)lane;
                         items             = e.ncols * shh;
                         mk                = true;
@@ -4557,7 +4625,7 @@ __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(HM
                 const int it    = it4 >> 2;
                 const HSrch1 &e = sh.u.a.s1[find_search(sh.u.a.s1, nsrch, it)];
                 const int local = it - e.item0;
-                const int y = mdiv(local, e.ncm), col = local - y * e.ncols;
+                const int y = rdiv(local, e.ncr), col = local - y * e.ncols;
                 const unsigned long long kk = hme_tile32q<decltype(fullk)::value>(e.a0, pstride, HQ1 * col, e.sh,
                                                                                   e.sa_w, y, kh1, sh.u.a.src4);
                 if ((it4 & 3) == 0 && kk != ~0ull)
@@ -4601,7 +4669,7 @@ __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(HM
                         e.a0              = w0 - e.sh;
                         e.sa_w            = sw;
                         e.ncols           = (int16_t)((((sw + 3) >> 2) + HQ - 1) / HQ); // realigned rows
-                        e.ncm             = magic_u32((uint32_t)e.ncols);
+                        e.ncr             = rdiv_of(e.ncols);
                         e.id              = (uint8_t)lane;
                         items             = e.ncols * shh;
                         mk                = true;
@@ -4629,7 +4697,7 @@ __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(HM
                 const int it    = it8 >> 3;
                 const HSrch1 &e = sh.u.a.s1[find_search(sh.u.a.s1, nsrch, it)];
                 const int local = it - e.item0;
-                const int y = mdiv(local, e.ncm), col = local - y * e.ncols;
+                const int y = rdiv(local, e.ncr), col = local - y * e.ncols;
                 const unsigned long long kk = hme_tile64(e.a0, pstride, HQ * col, e.sh, e.sa_w, y, kh2, sh.u.a.src1);
                 if ((it8 & 7) == 0 && kk != ~0ull)
                     atomicMin(&sh.u.a.key1[e.id], kk);
