@@ -2,7 +2,7 @@
 # svtme_stages.hip) taken from git revision REV (default HEAD) -- the "A" side of
 # an A/B against the working tree. FILES=all takes every source and header of csrc/ as REV has
 # them, a file REV does not have included: the library of REV itself.
-# usage: REV=HEAD NAME=base [FILES="svtme_host.cpp"] [SED='s/#define HT16 3/#define HT16 4/'] bash scripts/build_ab_lib.sh
+# usage: REV=HEAD NAME=base [FILES="svtme_submit.cpp"] [SED='s/#define HT16 3/#define HT16 4/'] bash scripts/build_ab_lib.sh
 # (SED: a sed expression applied to the copy of svtme_stages.hip, for one-constant experiments)
 set -e
 cd "$(dirname "$0")/.."

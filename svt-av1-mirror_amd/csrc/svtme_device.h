@@ -1,5 +1,5 @@
 // svtme_device.h — device-side layouts shared by the HIP kernels and the host
-// launcher (svtme_host.cpp). gfx950 (MI355X) only.
+// code (svtme_ctx.h and its files). gfx950 (MI355X) only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -233,3 +233,13 @@ struct TffcArgs {
     uint32_t n, sbs, pic_w_b64;
     int32_t W, H;                                  // the 8-aligned luma size
 };
+
+// Bytes per unit (one reference's SB) of the temporal filter's scratch sections, as svtme_tff.hip
+// indexes them; the host lays the sections out by these (TfScratch, svtme_windows.cpp).
+#define SVTME_TFF_TILE_BYTES 4096   // luma prediction: k_tff_pred / k_tff_norm, `A.tile + unit * 4096`
+#define SVTME_TFF_WGT_BYTES 64      // luma weights: `A.wgt[unit * 16 + ...]`, 16 dwords
+#define SVTME_TFF_E32_BYTES 16      // 32x32 errors: `A.e32[unit * 4 + ...]`, 4 dwords
+#define SVTME_TFFC_TILE_BYTES 2048  // Cb and Cr predictions: k_tff_pred_uv / k_tff_norm_uv, `A.tile + unit * 2048`
+#define SVTME_TFFC_WGT_BYTES 128    // chroma weights: `A.wgt[unit * 32 + ...]`, 32 dwords
+#define SVTME_TFFC_PLANE_SB_BYTES 1024 // one SB of one dense chroma plane: k_tff_norm_uv, `pl * A.sbs * 1024`
+// (the dense luma plane of k_tff_norm holds SVTME_TFF_TILE_BYTES per SB: whole 64 x 64 SBs)

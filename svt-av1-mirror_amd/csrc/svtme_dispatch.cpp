@@ -86,7 +86,7 @@ static void fp_area_bound(const svtme_controls *c, uint32_t *w, uint32_t *h) {
     *w = mw;
     *h = mh;
 }
-// the same bound for job validation (svtme_host.cpp)
+// the same bound for job validation (svtme_submit.cpp)
 extern "C" void svtme_fp_area_bound(const svtme_controls *c, uint32_t *w, uint32_t *h) { fp_area_bound(c, w, h); }
 
 // Per-slot search parameters of k_hme that do not depend on the SB: the
@@ -291,7 +291,7 @@ extern "C" void svtme_launch_plan_group(const DevJob *h_jobs, uint32_t n, Launch
         p->kernel[SLOT_E] = K_NONE;
 }
 
-// Batch launch key: jobs launched together must agree on it (svtme_host.cpp splits a batch into
+// Batch launch key: jobs launched together must agree on it (svtme_submit.cpp splits a batch into
 // groups by it). The plan without the two reducible facts: 5 bits per slot, rt_round, cls.
 extern "C" uint32_t svtme_launch_key(const DevJob *dj) {
     static_assert(K_COUNT <= 32, "a kernel id in 5 bits of the launch key");

@@ -1,5 +1,5 @@
 // svtme_launch.h — the launch boundary inside libsvtme.so: every launcher and primer the .hip
-// files define for svtme_host.cpp, and the host dispatch of the picture job
+// files define for the host files (svtme_ctx.h), and the host dispatch of the picture job
 // (svtme_dispatch.cpp). Included by the callers and by every file that defines one of these
 // functions, so a declaration that drifts from its definition does not compile. Internal: none
 // of this is part of include/svtme.h.

@@ -1,0 +1,468 @@
+// svtme_windows.cpp — the calls over a window of resident pictures, all on lane 0: the dynamic-GOP
+// detector (svtme_dg.hip) and temporal filtering's stages (svtme_tfsp.hip, svtme_tff.hip), alone
+// and as one window resident to resident. Each holds the context lock from its first launch to
+// its last copy, as svtme_submit_picture does: the device outputs are the context's, and a
+// release / invalidate of a picture from another thread waits for the lock.
+#include <cstring>
+
+#include "svtme_ctx.h"
+
+using namespace svtme_host;
+
+// ---- dynamic-GOP detector (dg_detector_hme_level0 / early_hme, pd_process.c:492-634) ----
+extern "C" svtme_status svtme_dg_detect(svtme_ctx *c, const svtme_dg_pair *pairs, uint32_t n, uint16_t sa_width,
+                                        uint16_t sa_height, svtme_dg_metrics *metrics, svtme_dg_sb *sb_out) {
+    if (!c || !pairs || !metrics)
+        return fail(SVTME_ERR_BAD_PARAMETER, "svtme_dg_detect: null ctx, pairs or metrics");
+    if (n < 1 || n > SVTME_DG_MAX_PAIRS)
+        return fail(SVTME_ERR_BAD_PARAMETER, "svtme_dg_detect: %u pairs (1..%d)", n, SVTME_DG_MAX_PAIRS);
+    if (!sa_width || !sa_height || ((sa_width + 7u) & ~7u) > SVTME_DG_MAX_SA || sa_height > SVTME_DG_MAX_SA)
+        return fail(SVTME_ERR_BAD_PARAMETER, "svtme_dg_detect: search area %ux%u (1..%d, the width rounded up to 8)",
+                    sa_width, sa_height, SVTME_DG_MAX_SA);
+    std::lock_guard<std::mutex> lk(c->mu);
+    PicBuf *pb[2 * SVTME_DG_MAX_PAIRS]; // pair k: the current picture at 2k, the reference at 2k + 1
+    for (uint32_t k = 0; k < n; k++) {
+        const uint64_t pn[2] = {pairs[k].cur_picture_number, pairs[k].ref_picture_number};
+        PicBuf **pk          = pb + 2 * k;
+        for (int i = 0; i < 2; i++)
+            if (!(pk[i] = find_pic(c, pn[i])))
+                return fail(SVTME_ERR_BAD_PARAMETER, "svtme_dg_detect: picture %llu is not resident",
+                            (unsigned long long)pn[i]);
+        if (pk[0]->W != pk[1]->W || pk[0]->H != pk[1]->H)
+            return fail(SVTME_ERR_BAD_PARAMETER, "svtme_dg_detect: pair %u: picture %llu is %ux%u, picture %llu %ux%u", k,
+                        (unsigned long long)pn[0], pk[0]->W, pk[0]->H, (unsigned long long)pn[1], pk[1]->W, pk[1]->H);
+        if (pk[0]->W != pb[0]->W || pk[0]->H != pb[0]->H)
+            return fail(SVTME_ERR_BAD_PARAMETER, "svtme_dg_detect: pair %u is %ux%u, pair 0 %ux%u: one size per call", k,
+                        pk[0]->W, pk[0]->H, pb[0]->W, pb[0]->H);
+    }
+    const uint32_t W = pb[0]->W, H = pb[0]->H, sbs = svtme_sb_total(W, H);
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t acc_bytes = sizeof(svtme_dg_metrics) * SVTME_DG_MAX_PAIRS;
+    svtme_status st        = ensure_buf(&c->d_dg, &c->dg_cap, acc_bytes + sizeof(svtme_dg_sb) * (size_t)n * sbs);
+    if (st)
+        return st;
+    DevPlane cur[SVTME_DG_MAX_PAIRS], ref[SVTME_DG_MAX_PAIRS];
+    for (uint32_t k = 0; k < 2 * n; k++) {
+        if ((st = join_upload(c, *pb[k], 0)))
+            return st;
+        (k & 1 ? ref : cur)[k / 2] = pb[k]->pyr.lv[2];
+    }
+    Lane &L               = c->lanes[0];
+    svtme_dg_metrics *d_m = (svtme_dg_metrics *)c->d_dg;
+    svtme_dg_sb *d_sb     = (svtme_dg_sb *)((uint8_t *)c->d_dg + acc_bytes);
+    HIP_TRY(hipMemsetAsync(d_m, 0, sizeof(svtme_dg_metrics) * n, L.s));
+    HIP_TRY(svtme_launch_dg(cur, ref, n, W, H, sa_width, sa_height, d_m, d_sb, L.s));
+    hipEvent_t done;
+    if ((st = submission_done(L, &done)))
+        return st;
+    mark_read(pb, 2 * n, 0, done);
+    HIP_TRY(hipMemcpyAsync(metrics, d_m, sizeof(svtme_dg_metrics) * n, hipMemcpyDeviceToHost, L.s));
+    if (sb_out)
+        HIP_TRY(hipMemcpyAsync(sb_out, d_sb, sizeof(svtme_dg_sb) * (size_t)n * sbs, hipMemcpyDeviceToHost, L.s));
+    HIP_TRY(hipStreamSynchronize(L.s));
+    for (uint32_t k = 0; k < n; k++) svtme_dg_finish(W, H, &metrics[k]);
+    return SVTME_OK;
+}
+
+// ---- what the temporal-filter calls share ----
+// The resident pictures pn[0..count) of a window, each W x H (8-aligned) and, where the call
+// filters chroma, with chroma attached. The first picture that fails decides the message.
+static svtme_status resident_pics(svtme_ctx *c, const char *fn, const uint64_t *pn, uint32_t count, uint32_t W,
+                                  uint32_t H, bool chroma, PicBuf **pb) {
+    for (uint32_t k = 0; k < count; k++) {
+        if (!(pb[k] = find_pic(c, pn[k])))
+            return fail(SVTME_ERR_BAD_PARAMETER, "%s: picture %llu is not resident", fn, (unsigned long long)pn[k]);
+        if (pb[k]->W != W || pb[k]->H != H)
+            return fail(SVTME_ERR_BAD_PARAMETER, "%s: picture %llu is %ux%u, the window %ux%u", fn,
+                        (unsigned long long)pn[k], pb[k]->W, pb[k]->H, W, H);
+        if (chroma && !pb[k]->cmem)
+            return fail(SVTME_ERR_BAD_PARAMETER, "%s: picture %llu has no chroma", fn, (unsigned long long)pn[k]);
+    }
+    return SVTME_OK;
+}
+
+// lane 0 waits for the uploads of the centre pb[0] and the n references behind it; ref[k]: level 0 of reference k
+static svtme_status join_window(svtme_ctx *c, PicBuf *const *pb, uint32_t n, DevPlane *ref) {
+    for (uint32_t k = 0; k <= n; k++) {
+        svtme_status st = join_upload(c, *pb[k], 0);
+        if (st)
+            return st;
+        if (k)
+            ref[k - 1] = pb[k]->pyr.lv[0];
+    }
+    return SVTME_OK;
+}
+
+// the ranges of the two stages' controls; `what` names them in the message ("controls" where the
+// call has one set, "sub-pel controls" / "filter controls" in the window call)
+static svtme_status tfsp_controls_check(const char *fn, const char *what, const svtme_tf_subpel_controls *ctl) {
+    if (ctl->half_pel_mode <= 3 && ctl->quarter_pel_mode <= 3 && ctl->eight_pel_mode <= 1 && ctl->use_2tap <= 1 &&
+        ctl->sub_sampling_shift <= 1 && ctl->enable_8x8_pred <= 1)
+        return SVTME_OK;
+    return fail(SVTME_ERR_BAD_PARAMETER,
+                "%s: %s out of range: half %u quarter %u (0..3), eighth %u, use_2tap %u, "
+                "sub_sampling_shift %u, enable_8x8_pred %u (0..1)", fn, what,
+                ctl->half_pel_mode, ctl->quarter_pel_mode, ctl->eight_pel_mode, ctl->use_2tap,
+                ctl->sub_sampling_shift, ctl->enable_8x8_pred);
+}
+static svtme_status tff_controls_check(const char *fn, const char *what, const svtme_tf_filter_controls *ctl) {
+    if (ctl->tf_mv_dist_th <= 32767 && ctl->sub_sampling_shift <= 1)
+        return SVTME_OK;
+    return fail(SVTME_ERR_BAD_PARAMETER, "%s: %s out of range: tf_mv_dist_th %u (0..32767), sub_sampling_shift %u (0..1)",
+                fn, what, ctl->tf_mv_dist_th, ctl->sub_sampling_shift);
+}
+
+// The filter's scratch in c->d_tff, n references over sbs SBs (units = n x sbs):
+//   results of the sub-pel stage | luma tiles | weights | errors | (dense) the luma plane, whole SBs |
+//   (chroma) Cb and Cr tiles | weights | (chroma, dense) the two planes, whole SBs
+// (704 bytes a result, multiples of 16 per unit or SB elsewhere: the sections stay 16-byte aligned).
+// The stage calls copy dense planes out; the window call writes the result picture and has none.
+struct TfScratch {
+    svtme_tf_subpel_sb *sub;
+    uint8_t *tile, *plane;   // plane: dense only
+    uint32_t *wgt, *e32;
+    uint8_t *ctile, *cplane; // chroma only, as cwgt; cplane: Cb then Cr, cplane_bytes each, dense only
+    uint32_t *cwgt;
+    size_t sub_bytes, e32_bytes, cplane_bytes;
+};
+static svtme_status tf_scratch(svtme_ctx *c, uint32_t n, uint32_t sbs, bool dense, bool chroma, TfScratch *S) {
+    const size_t units = (size_t)n * sbs;
+    S->sub_bytes    = sizeof(svtme_tf_subpel_sb) * units;
+    S->e32_bytes    = SVTME_TFF_E32_BYTES * units;
+    S->cplane_bytes = (size_t)SVTME_TFFC_PLANE_SB_BYTES * sbs;
+    size_t end = 0;
+    auto take  = [&end](bool present, size_t bytes) { // the section's offset; absent sections are empty
+        const size_t at = end;
+        end += present ? bytes : 0;
+        return at;
+    };
+    const size_t o_sub = take(true, S->sub_bytes), o_tile = take(true, SVTME_TFF_TILE_BYTES * units),
+                 o_wgt = take(true, SVTME_TFF_WGT_BYTES * units), o_e32 = take(true, S->e32_bytes),
+                 o_plane = take(dense, (size_t)SVTME_TFF_TILE_BYTES * sbs),
+                 o_ctile = take(chroma, SVTME_TFFC_TILE_BYTES * units),
+                 o_cwgt = take(chroma, SVTME_TFFC_WGT_BYTES * units),
+                 o_cplane = take(chroma && dense, 2 * S->cplane_bytes);
+    svtme_status st = ensure_buf(&c->d_tff, &c->tff_cap, end);
+    if (st)
+        return st;
+    uint8_t *base = (uint8_t *)c->d_tff;
+    S->sub = (svtme_tf_subpel_sb *)(base + o_sub), S->tile = base + o_tile, S->plane = base + o_plane;
+    S->wgt = (uint32_t *)(base + o_wgt), S->e32 = (uint32_t *)(base + o_e32);
+    S->ctile = base + o_ctile, S->cplane = base + o_cplane, S->cwgt = (uint32_t *)(base + o_cwgt);
+    return SVTME_OK;
+}
+
+// the chroma side of svtme_tf_filter_yuv / svtme_tf_window_yuv: the decay factors and the host copies
+struct TfChroma {
+    uint32_t decay[2];
+    uint8_t *out[2]; // Cb, Cr; either may be NULL
+    uint32_t stride[2];
+};
+
+// checked before any GPU work: a stride under the chroma width
+static svtme_status chroma_strides_ok(const char *fn, const TfChroma *uv, uint32_t width) {
+    for (int p = 0; p < 2; p++)
+        if (uv->out[p] && uv->stride[p] < (width + 1) >> 1)
+            return fail(SVTME_ERR_BAD_PARAMETER, "%s: %s stride %u under the chroma width %u", fn, p ? "cr" : "cb",
+                        uv->stride[p], (width + 1) >> 1);
+    return SVTME_OK;
+}
+
+// the chroma stage's arguments over the scratch of a call with chroma
+static void tffc_fill(TffcArgs &A, PicBuf *const *pb, uint32_t n, uint32_t W, uint32_t H,
+                      const svtme_tf_filter_controls *ctl, const TfChroma *uv, const TfScratch &S) {
+    A.cen_y = pb[0]->pyr.lv[0];
+    for (int p = 0; p < 2; p++) {
+        A.cen[p] = pb[0]->chroma[p];
+        for (uint32_t k = 0; k < SVTME_MAX_BATCH_JOBS; k++) A.ref[p][k] = pb[k < n ? k + 1 : 1]->chroma[p].base;
+    }
+    A.ref_stride = pb[1]->chroma[0].stride;
+    A.sub        = S.sub;
+    A.tile_y     = S.tile;
+    A.e32        = S.e32;
+    A.tile       = S.ctile;
+    A.wgt        = S.cwgt;
+    A.plane      = S.cplane;
+    A.decay_cb   = uv->decay[0];
+    A.decay_cr   = uv->decay[1];
+    A.dist_th    = ctl->tf_mv_dist_th;
+    A.n          = n;
+    A.pic_w_b64  = (W + 63) / 64;
+    A.sbs        = svtme_sb_total(W, H);
+    A.W          = (int32_t)W;
+    A.H          = (int32_t)H;
+}
+
+// ---- Temporal filtering's sub-pel refinement (svtme_tfsp.hip) ----
+extern "C" svtme_status svtme_tf_subpel(svtme_ctx *c, uint64_t centre_picture_number,
+                                        const uint64_t *ref_picture_numbers, uint32_t n, uint32_t width,
+                                        uint32_t height, const svtme_tf_subpel_controls *ctl,
+                                        const svtme_ref_record *records, svtme_tf_subpel_sb *out) {
+    const char *fn = "svtme_tf_subpel";
+    if (!c || !ref_picture_numbers || !ctl || !records || !out)
+        return fail(SVTME_ERR_BAD_PARAMETER, "%s: null ctx, ref_picture_numbers, controls, records or out", fn);
+    if (n < 1 || n > SVTME_MAX_BATCH_JOBS)
+        return fail(SVTME_ERR_BAD_PARAMETER, "%s: %u references (1..%d)", fn, n, SVTME_MAX_BATCH_JOBS);
+    svtme_status st;
+    if ((st = tfsp_controls_check(fn, "controls", ctl)))
+        return st;
+    if (!width || !height)
+        return fail(SVTME_ERR_BAD_PARAMETER, "%s: %ux%u picture", fn, width, height);
+    const uint32_t W = svtme_align8_u(width), H = svtme_align8_u(height);
+    uint64_t pn[SVTME_MAX_BATCH_JOBS + 1] = {centre_picture_number};
+    memcpy(pn + 1, ref_picture_numbers, n * sizeof(uint64_t));
+    std::lock_guard<std::mutex> lk(c->mu);
+    PicBuf *pb[SVTME_MAX_BATCH_JOBS + 1];
+    if ((st = resident_pics(c, fn, pn, n + 1, W, H, false, pb)))
+        return st;
+    const uint32_t sbs = svtme_sb_total(W, H);
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t rec_bytes = sizeof(svtme_ref_record) * (size_t)n * sbs;
+    const size_t out_bytes = sizeof(svtme_tf_subpel_sb) * (size_t)n * sbs;
+    DevPlane ref[SVTME_MAX_BATCH_JOBS];
+    if ((st = ensure_buf(&c->d_tfsp, &c->tfsp_cap, rec_bytes + out_bytes)) || (st = join_window(c, pb, n, ref)))
+        return st;
+    Lane &L                   = c->lanes[0];
+    svtme_ref_record *d_rec   = (svtme_ref_record *)c->d_tfsp;
+    svtme_tf_subpel_sb *d_out = (svtme_tf_subpel_sb *)((uint8_t *)c->d_tfsp + rec_bytes);
+    HIP_TRY(hipMemcpyAsync(d_rec, records, rec_bytes, hipMemcpyHostToDevice, L.s));
+    HIP_TRY(svtme_launch_tfsp(&pb[0]->pyr.lv[0], ref, n, W, H, ctl, d_rec, d_out, L.s));
+    hipEvent_t done;
+    if ((st = submission_done(L, &done)))
+        return st;
+    mark_read(pb, n + 1, 0, done);
+    HIP_TRY(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, L.s));
+    HIP_TRY(hipStreamSynchronize(L.s));
+    return SVTME_OK;
+}
+
+// ---- Temporal filtering's prediction and weighting (svtme_tff.hip) ----
+// svtme_tf_filter (uv NULL) and svtme_tf_filter_yuv
+static svtme_status tf_filter_impl(const char *fn, const TfChroma *uv, svtme_ctx *c, uint64_t centre_picture_number,
+                                   const uint64_t *ref_picture_numbers, uint32_t n, uint32_t width, uint32_t height,
+                                   const svtme_tf_filter_controls *ctl, const svtme_tf_subpel_sb *subpel, uint8_t *out,
+                                   uint32_t out_stride, uint32_t *err32_out) {
+    if (!c || !ref_picture_numbers || !ctl || !subpel || !out)
+        return fail(SVTME_ERR_BAD_PARAMETER, "%s: null ctx, ref_picture_numbers, controls, subpel or out", fn);
+    if (n < 1 || n > SVTME_MAX_BATCH_JOBS)
+        return fail(SVTME_ERR_BAD_PARAMETER, "%s: %u references (1..%d)", fn, n, SVTME_MAX_BATCH_JOBS);
+    svtme_status st;
+    if ((st = tff_controls_check(fn, "controls", ctl)))
+        return st;
+    if (!width || !height)
+        return fail(SVTME_ERR_BAD_PARAMETER, "%s: %ux%u picture", fn, width, height);
+    if (out_stride < width)
+        return fail(SVTME_ERR_BAD_PARAMETER, "%s: out_stride %u under the width %u", fn, out_stride, width);
+    if (uv && (st = chroma_strides_ok(fn, uv, width)))
+        return st;
+    const uint32_t W = svtme_align8_u(width), H = svtme_align8_u(height);
+    const uint32_t sbs = svtme_sb_total(W, H);
+    for (size_t k = 0; k < (size_t)n * sbs; k++)
+        if (subpel[k].branch > SVTME_TFSP_32)
+            return fail(SVTME_ERR_BAD_PARAMETER, "%s: subpel[%zu].branch is %u (0..2)", fn, k, subpel[k].branch);
+    uint64_t pn[SVTME_MAX_BATCH_JOBS + 1] = {centre_picture_number};
+    memcpy(pn + 1, ref_picture_numbers, n * sizeof(uint64_t));
+    std::lock_guard<std::mutex> lk(c->mu);
+    PicBuf *pb[SVTME_MAX_BATCH_JOBS + 1];
+    if ((st = resident_pics(c, fn, pn, n + 1, W, H, uv != nullptr, pb)))
+        return st;
+    HIP_TRY(hipSetDevice(c->device));
+    TfScratch S;
+    DevPlane ref[SVTME_MAX_BATCH_JOBS];
+    if ((st = tf_scratch(c, n, sbs, true, uv != nullptr, &S)) || (st = join_window(c, pb, n, ref)))
+        return st;
+    Lane &L              = c->lanes[0];
+    const size_t pstride = (size_t)((W + 63) / 64) * 64; // of the dense luma plane; the chroma planes' is half
+    HIP_TRY(hipMemcpyAsync(S.sub, subpel, S.sub_bytes, hipMemcpyHostToDevice, L.s));
+    HIP_TRY(svtme_launch_tff(&pb[0]->pyr.lv[0], ref, n, W, H, ctl, S.sub, S.tile, S.wgt, S.e32, S.plane, L.s));
+    if (uv) {
+        TffcArgs U{};
+        tffc_fill(U, pb, n, W, H, ctl, uv, S);
+        HIP_TRY(svtme_launch_tffc(&U, L.s));
+    }
+    hipEvent_t done;
+    if ((st = submission_done(L, &done)))
+        return st;
+    mark_read(pb, n + 1, 0, done);
+    HIP_TRY(hipMemcpy2DAsync(out, out_stride, S.plane, pstride, width, height, hipMemcpyDeviceToHost, L.s));
+    if (err32_out)
+        HIP_TRY(hipMemcpyAsync(err32_out, S.e32, S.e32_bytes, hipMemcpyDeviceToHost, L.s));
+    for (int p = 0; uv && p < 2; p++)
+        if (uv->out[p])
+            HIP_TRY(hipMemcpy2DAsync(uv->out[p], uv->stride[p], S.cplane + p * S.cplane_bytes, pstride / 2,
+                                     (width + 1) >> 1, (height + 1) >> 1, hipMemcpyDeviceToHost, L.s));
+    HIP_TRY(hipStreamSynchronize(L.s));
+    return SVTME_OK;
+}
+
+extern "C" svtme_status svtme_tf_filter(svtme_ctx *c, uint64_t centre_picture_number,
+                                        const uint64_t *ref_picture_numbers, uint32_t n, uint32_t width,
+                                        uint32_t height, const svtme_tf_filter_controls *ctl,
+                                        const svtme_tf_subpel_sb *subpel, uint8_t *out, uint32_t out_stride,
+                                        uint32_t *err32_out) {
+    return tf_filter_impl("svtme_tf_filter", nullptr, c, centre_picture_number, ref_picture_numbers, n, width, height,
+                          ctl, subpel, out, out_stride, err32_out);
+}
+
+extern "C" svtme_status svtme_tf_filter_yuv(svtme_ctx *c, uint64_t centre_picture_number,
+                                            const uint64_t *ref_picture_numbers, uint32_t n, uint32_t width,
+                                            uint32_t height, const svtme_tf_filter_yuv_controls *ctl,
+                                            const svtme_tf_subpel_sb *subpel, const svtme_tf_filter_yuv_out *out) {
+    if (!ctl || !out)
+        return fail(SVTME_ERR_BAD_PARAMETER, "svtme_tf_filter_yuv: null controls or out");
+    const TfChroma uv = {{ctl->tf_decay_factor_cb_fp16, ctl->tf_decay_factor_cr_fp16},
+                         {out->cb, out->cr},
+                         {out->cb_stride, out->cr_stride}};
+    return tf_filter_impl("svtme_tf_filter_yuv", &uv, c, centre_picture_number, ref_picture_numbers, n, width, height,
+                          &ctl->luma, subpel, out->y, out->y_stride, out->err32);
+}
+
+// ----------------------------------------------------------------------------
+// One temporal-filtering window, resident to resident: the TF-ME batch, k_tfsp,
+// k_tff_pred and the normalisation into the result picture, chained by lane 0's
+// stream through the two stages' scratch.
+// ----------------------------------------------------------------------------
+// svtme_tf_window (uv NULL) and svtme_tf_window_yuv
+static svtme_status tf_window_impl(const char *fn, const TfChroma *uv, svtme_ctx *c, const svtme_job *jobs, uint32_t n,
+                                   uint32_t src_width, uint32_t src_height, const svtme_tf_subpel_controls *sp_ctl,
+                                   const svtme_tf_filter_controls *f_ctl, uint64_t out_pn,
+                                   const svtme_tf_window_out *out) {
+    if (!c || !jobs || !sp_ctl || !f_ctl)
+        return fail(SVTME_ERR_BAD_PARAMETER, "%s: null ctx, jobs, subpel_controls or filter_controls", fn);
+    if (n < 1 || n > SVTME_MAX_BATCH_JOBS)
+        return fail(SVTME_ERR_BAD_PARAMETER, "%s: %u jobs (1..%d)", fn, n, SVTME_MAX_BATCH_JOBS);
+    const uint32_t W = jobs[0].width, H = jobs[0].height;
+    if (!W || !H || (W & 7) || (H & 7) || W > 16384 || H > 16384)
+        return fail(SVTME_ERR_BAD_PARAMETER, "%s: job size %ux%u must be a non-zero multiple of 8, "
+                                             "16384 at the most", fn, W, H);
+    const uint32_t sbs = svtme_sb_total(W, H);
+    for (uint32_t k = 0; k < n; k++) {
+        const svtme_job &j = jobs[k];
+        if (j.me_type != SVTME_ME_MCTF || j.num_lists != 1 || j.num_refs[0] != 1)
+            return fail(SVTME_ERR_BAD_PARAMETER,
+                        "%s: job %u: me_type %u, %u lists, %u references (SVTME_ME_MCTF, one list, one "
+                        "reference)", fn, k, j.me_type, j.num_lists, j.num_refs[0]);
+        if (j.picture_number != jobs[0].picture_number)
+            return fail(SVTME_ERR_BAD_PARAMETER, "%s: job %u's centre is picture %llu, job 0's %llu", fn, k,
+                        (unsigned long long)j.picture_number, (unsigned long long)jobs[0].picture_number);
+        if (j.width != W || j.height != H)
+            return fail(SVTME_ERR_BAD_PARAMETER, "%s: job %u is %ux%u, job 0 %ux%u", fn, k, j.width, j.height,
+                        W, H);
+        if (j.sb_begin != 0 || (j.sb_count != 0 && j.sb_count != sbs))
+            return fail(SVTME_ERR_BAD_PARAMETER, "%s: job %u covers SBs [%u, %u) of %u: the whole picture "
+                                                 "only", fn, k, j.sb_begin, j.sb_begin + j.sb_count, sbs);
+    }
+    if (!src_width || !src_height || svtme_align8_u(src_width) != W || svtme_align8_u(src_height) != H)
+        return fail(SVTME_ERR_BAD_PARAMETER, "%s: source size %ux%u does not align to the jobs' %ux%u", fn,
+                    src_width, src_height, W, H);
+    if (out && out->plane && out->plane_stride < src_width)
+        return fail(SVTME_ERR_BAD_PARAMETER, "%s: plane_stride %u under the width %u", fn, out->plane_stride,
+                    src_width);
+    svtme_status st;
+    if ((uv && (st = chroma_strides_ok(fn, uv, src_width))) || (st = tfsp_controls_check(fn, "sub-pel controls", sp_ctl)) ||
+        (st = tff_controls_check(fn, "filter controls", f_ctl)))
+        return st;
+    uint64_t pn[SVTME_MAX_BATCH_JOBS + 1] = {jobs[0].picture_number};
+    for (uint32_t k = 0; k < n; k++) {
+        pn[k + 1] = jobs[k].ref_picture_number[0][0];
+        if (pn[k + 1] == out_pn)
+            return fail(SVTME_ERR_BAD_PARAMETER, "%s: the result picture %llu is job %u's reference", fn,
+                        (unsigned long long)out_pn, k);
+    }
+    std::lock_guard<std::mutex> lk(c->mu);
+    // The batch checks the same; here before the result picture is made. The pointers hold across
+    // the batch and the result picture's allocation: std::map keeps its other nodes where they
+    // are, and the result picture, where it is the centre, has the centre's size and stays too.
+    PicBuf *pb[SVTME_MAX_BATCH_JOBS + 1];
+    if ((st = resident_pics(c, fn, pn, n + 1, W, H, uv != nullptr, pb)))
+        return st;
+    HIP_TRY(hipSetDevice(c->device));
+    // the sub-pel scratch holds the records (its results go to the filter's scratch)
+    const size_t rec_bytes = sizeof(svtme_ref_record) * (size_t)n * sbs;
+    TfScratch S;
+    if ((st = ensure_buf(&c->d_tfsp, &c->tfsp_cap, rec_bytes)) || (st = tf_scratch(c, n, sbs, false, uv != nullptr, &S)))
+        return st;
+    svtme_ref_record *d_rec = (svtme_ref_record *)c->d_tfsp;
+    // the TF-ME jobs: one batch, job k's records (R = 1) at d_rec + k x SBs, the array k_tfsp reads
+    svtme_ref_record *recs_of[SVTME_MAX_BATCH_JOBS];
+    for (uint32_t k = 0; k < n; k++) recs_of[k] = d_rec + (size_t)k * sbs;
+    if ((st = submit_batch_locked(c, jobs, n, recs_of, nullptr, false, 0)))
+        return st;
+    // the result picture (a new number: a buffer of the pool)
+    PicBuf *po;
+    if ((st = alloc_pic(c, out_pn, W, H, &po, uv != nullptr)) || (uv && (st = alloc_chroma(c, *po))))
+        return st;
+    Lane &L = c->lanes[0];
+    DevPlane ref[SVTME_MAX_BATCH_JOBS];
+    for (uint32_t k = 0; k < n; k++) ref[k] = pb[k + 1]->pyr.lv[0]; // (joined to lane 0 by the batch)
+    // its old planes, if it had any: an upload still running, readers queued on the other lanes
+    if ((st = join_upload(c, *po, 0)) || (st = after_readers(c, *po, L.s)))
+        return st;
+    HIP_TRY(svtme_launch_tfsp(&pb[0]->pyr.lv[0], ref, n, W, H, sp_ctl, d_rec, S.sub, L.s));
+    if (uv) {
+        // both predictions before either normalisation: in place the chroma stage reads the centre's luma
+        TffcArgs U{};
+        tffc_fill(U, pb, n, W, H, f_ctl, uv, S);
+        U.dst[0] = po->chroma[0], U.dst[1] = po->chroma[1];
+        HIP_TRY(svtme_launch_tff_pic_yuv(&pb[0]->pyr.lv[0], ref, n, W, H, f_ctl, S.sub, S.tile, S.wgt, S.e32,
+                                         &po->pyr.lv[0], &U, L.s));
+    } else
+        HIP_TRY(svtme_launch_tff_pic(&pb[0]->pyr.lv[0], ref, n, W, H, f_ctl, S.sub, S.tile, S.wgt, S.e32,
+                                     &po->pyr.lv[0], L.s));
+    // the sub-8 re-pad and the margins from the plane's own interior, then levels 1 and 2
+    if ((st = build_pyramid(c, po, po->pyr.lv[0].base, (uint32_t)po->pyr.lv[0].stride, src_width, src_height, 0, L.s)))
+        return st;
+    // the chroma planes likewise: beyond the true chroma size and the margins, from their own interior
+    for (int p = 0; uv && p < 2; p++)
+        if ((st = build_chroma(po, p, po->chroma[p].base, (uint32_t)po->chroma[p].stride, (src_width + 1) >> 1,
+                               (src_height + 1) >> 1, L.s)))
+            return st;
+    hipEvent_t done;
+    if ((st = submission_done(L, &done)))
+        return st;
+    mark_read(pb, n + 1, 0, done);
+    po->used[0] = done; // a later upload under its number waits for the window
+    // the other lanes' later readers wait for the window as they do for an asynchronous upload
+    if (!po->ready)
+        HIP_TRY(hipEventCreateWithFlags(&po->ready, hipEventDisableTiming));
+    if ((st = upload_publish(*po, L.s, kAllLanes & ~1u)))
+        return st;
+    const bool want_uv = uv && (uv->out[0] || uv->out[1]);
+    if (!want_uv && (!out || (!out->plane && !out->records && !out->subpel && !out->err32)))
+        return SVTME_OK;
+    if (out && out->records)
+        HIP_TRY(hipMemcpyAsync(out->records, d_rec, rec_bytes, hipMemcpyDeviceToHost, L.s));
+    if (out && out->subpel)
+        HIP_TRY(hipMemcpyAsync(out->subpel, S.sub, S.sub_bytes, hipMemcpyDeviceToHost, L.s));
+    if (out && out->err32)
+        HIP_TRY(hipMemcpyAsync(out->err32, S.e32, S.e32_bytes, hipMemcpyDeviceToHost, L.s));
+    if (out && out->plane)
+        HIP_TRY(hipMemcpy2DAsync(out->plane, out->plane_stride, po->pyr.lv[0].base, (size_t)po->pyr.lv[0].stride,
+                                 src_width, src_height, hipMemcpyDeviceToHost, L.s));
+    for (int p = 0; want_uv && p < 2; p++)
+        if (uv->out[p])
+            HIP_TRY(hipMemcpy2DAsync(uv->out[p], uv->stride[p], po->chroma[p].base, (size_t)po->chroma[p].stride,
+                                     (src_width + 1) >> 1, (src_height + 1) >> 1, hipMemcpyDeviceToHost, L.s));
+    HIP_TRY(hipStreamSynchronize(L.s));
+    return SVTME_OK;
+}
+
+extern "C" svtme_status svtme_tf_window(svtme_ctx *c, const svtme_job *jobs, uint32_t n, uint32_t src_width,
+                                        uint32_t src_height, const svtme_tf_subpel_controls *sp_ctl,
+                                        const svtme_tf_filter_controls *f_ctl, uint64_t out_pn,
+                                        const svtme_tf_window_out *out) {
+    return tf_window_impl("svtme_tf_window", nullptr, c, jobs, n, src_width, src_height, sp_ctl, f_ctl, out_pn, out);
+}
+
+extern "C" svtme_status svtme_tf_window_yuv(svtme_ctx *c, const svtme_job *jobs, uint32_t n, uint32_t src_width,
+                                            uint32_t src_height, const svtme_tf_subpel_controls *sp_ctl,
+                                            const svtme_tf_filter_yuv_controls *f_ctl, uint64_t out_pn,
+                                            const svtme_tf_window_out *out, const svtme_tf_window_yuv_out *out_uv) {
+    if (!f_ctl)
+        return fail(SVTME_ERR_BAD_PARAMETER, "svtme_tf_window_yuv: null filter_controls");
+    const TfChroma uv = {{f_ctl->tf_decay_factor_cb_fp16, f_ctl->tf_decay_factor_cr_fp16},
+                         {out_uv ? out_uv->cb : nullptr, out_uv ? out_uv->cr : nullptr},
+                         {out_uv ? out_uv->cb_stride : 0, out_uv ? out_uv->cr_stride : 0}};
+    return tf_window_impl("svtme_tf_window_yuv", &uv, c, jobs, n, src_width, src_height, sp_ctl, &f_ctl->luma, out_pn,
+                          out);
+}
