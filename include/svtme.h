@@ -786,6 +786,73 @@ svtme_status svtme_tf_window_yuv(svtme_ctx *ctx, const svtme_job *jobs, uint32_t
                                  const svtme_tf_filter_yuv_controls *filter_controls, uint64_t out_picture_number,
                                  const svtme_tf_window_out *out, const svtme_tf_window_yuv_out *out_uv);
 
+/* ---------------------------------------------------------------------------
+ * Temporal filtering of 10-bit luma (is_highbd in temporal_filtering.c). The
+ * TF-ME search and the sub-pel refinement of a 10-bit picture run on its MSB plane
+ * (svtme_picture_upload_10bit; every level of tf_controls sets use_8bit_subpel), so
+ * svtme_tf_subpel serves them as it is. What follows reads the full-precision
+ * pictures: the final MULTITAP_SHARP prediction (svt_highbd_inter_predictor, bd
+ * 10), the 32x32 errors of the 64x64 branches (svt_aom_highbd_10_variance32x32_c /
+ * 32x16_c), the weights (svt_av1_apply_temporal_filter_planewise_medium_hbd_c: the
+ * 8-bit function with the window SSE >> 4, the 16x16 block error >> 4 and the
+ * 32x32 block error >> 6 instead of >> 2), the accumulation and the normalisation
+ * into 16-bit samples. Luma, 10 bit, use_zz_based_filter == 0, use_8bit_subpel ==
+ * 1. Not served: 10-bit chroma, the high-bit-depth sub-pel search (use_8bit_subpel
+ * == 0), the zz filter, 12 bit.
+ * ------------------------------------------------------------------------- */
+/* Attach the full-precision luma (16-bit samples, values 0..1023, rows `stride`
+ * SAMPLES apart) to a picture that is already resident, normally one uploaded with
+ * svtme_picture_upload_10bit from the same samples: keeping the MSB plane p >> 2
+ * consistent with it is the caller's duty. width x height is the size the luma was
+ * uploaded with. The plane is a buffer of its own, replicated to the 8-aligned size
+ * and by SVTME_PAD_FULL on every side, which is what svt_aom_pack_highbd_pic makes
+ * of the reference's padded 8-bit and 2-bit planes. Synchronous, ordered after
+ * queued readers of the picture; released with the picture; any later luma upload,
+ * svtme_picture_invalidate, svtme_tf_window or svtme_tf_window_yuv result under the
+ * same number drops it. The 8-bit calls and the yuv calls never read it. Samples
+ * above 1023 are the caller's error: the results of the 10-bit calls are then
+ * unspecified, but no read or write leaves the buffers. Returns
+ * SVTME_ERR_BAD_PARAMETER before any GPU work for a NULL ctx / y, a zero size,
+ * stride < width, a picture that is not resident or of another aligned size. */
+svtme_status svtme_picture_attach_10bit(svtme_ctx *ctx, uint64_t picture_number, const uint16_t *y, uint32_t stride,
+                                        uint32_t width, uint32_t height);
+/* Copy the padded 16-bit plane back in the shape of svtme_picture_download for
+ * level 0: (height + 2 pad) rows of (width + 2 pad) samples, *stride in samples;
+ * dst NULL asks for the sizes alone. SVTME_ERR_BAD_PARAMETER for a NULL ctx, a
+ * picture that is not resident or has no 10-bit plane. */
+svtme_status svtme_picture_download_10bit(svtme_ctx *ctx, uint64_t picture_number, uint16_t *dst, uint32_t *stride,
+                                          uint32_t *width, uint32_t *height, uint32_t *pad);
+
+/* svtme_tf_filter on the attached 16-bit planes: the same arguments, `subpel` what
+ * svtme_tf_subpel returned on the MSB planes, `out` 16-bit samples with out_stride
+ * in samples, err32_out NULL or the 32x32 errors (64x64 branches: the 10-bit
+ * variance). No resident picture is modified. Synchronous. Refusals: those of
+ * svtme_tf_filter, and a picture of the window without an attached 10-bit plane. */
+svtme_status svtme_tf_filter_10bit(svtme_ctx *ctx, uint64_t centre_picture_number, const uint64_t *ref_picture_numbers,
+                                   uint32_t n, uint32_t width, uint32_t height,
+                                   const svtme_tf_filter_controls *controls, const svtme_tf_subpel_sb *subpel,
+                                   uint16_t *out, uint32_t out_stride, uint32_t *err32_out);
+
+/* svtme_tf_window for 10-bit pictures: the TF-ME batch and the sub-pel refinement on
+ * the MSB planes, then the 10-bit prediction, weighting and normalisation, chained on
+ * lane 0's stream through device memory. The result picture gets both planes: the
+ * filtered 16-bit plane inside the aligned size, re-padded beyond src_width x
+ * src_height with the margins written, as svtme_picture_attach_10bit of the filtered
+ * plane would leave it; and level 0 = filtered >> 2 (what svt_unpack_and_2bcompress
+ * writes as the 8-bit plane) with its re-pad, margins and levels 1 and 2 made as
+ * svtme_tf_window makes them: the picture is what svtme_picture_upload_10bit plus
+ * svtme_picture_attach_10bit of the filtered plane leave. Chroma attached to the
+ * result's number is dropped. out->plane receives the MSB plane; plane16 (NULL or
+ * rows plane16_stride SAMPLES apart, >= src_width) the 16-bit plane. In place, a
+ * fresh number, the ordering guarantees, the asynchronous return when no host copy
+ * is asked for and the refusals are svtme_tf_window's; refused too, before any GPU
+ * work, are plane16 set with plane16_stride < src_width and a picture of the window
+ * without an attached 10-bit plane. */
+svtme_status svtme_tf_window_10bit(svtme_ctx *ctx, const svtme_job *jobs, uint32_t n, uint32_t src_width,
+                                   uint32_t src_height, const svtme_tf_subpel_controls *subpel_controls,
+                                   const svtme_tf_filter_controls *filter_controls, uint64_t out_picture_number,
+                                   const svtme_tf_window_out *out, uint16_t *plane16, uint32_t plane16_stride);
+
 /* Number of 64x64 SBs of a width x height picture, and R for a job. */
 uint32_t svtme_sb_total(uint32_t width, uint32_t height);
 uint32_t svtme_job_ref_slots(const svtme_job *job);

@@ -2,7 +2,7 @@
 // of this is part of include/svtme.h.
 //
 //   svtme_ctx.cpp       error state, context create / destroy, lanes and streams, timing, host memory
-//   svtme_pictures.cpp  the picture pool, pyramid builds, every upload, release, download, chroma
+//   svtme_pictures.cpp  the picture pool, pyramid builds, every upload, release, download, chroma, 10-bit luma
 //   svtme_submit.cpp    job validation, the job-table ring, batch and packed submission, tickets, fetch
 //   svtme_windows.cpp   the picture-window calls: svtme_dg_detect and the temporal-filter stages
 //   svtme_controls.cpp  pure host code (no HIP): control derivation, the detector's reduction
@@ -31,6 +31,11 @@ struct PicBuf {
     uint8_t *cmem = nullptr;
     size_t cbytes = 0;
     DevPlane chroma[2]{}; // Cb, Cr
+    // attached full-precision luma of a 10-bit picture (svtme_picture_attach_10bit, svtme_tf_window_10bit):
+    // a buffer of its own as the chroma's is, 16-bit samples (svtme_hbd_geometry); nullptr: none
+    uint8_t *hmem = nullptr;
+    size_t hbytes = 0;
+    DevPlane hbd{};
     hipEvent_t ready = nullptr;          // end of an asynchronous upload on the upload stream
     uint32_t pending = 0;                 // lanes whose stream has not waited on `ready` yet
     hipEvent_t used[SVTME_LANES] = {};    // end of the last submission of each lane that reads the
@@ -184,8 +189,13 @@ inline svtme_status join_upload(svtme_ctx *c, PicBuf &pb, int lane) {
 svtme_status after_readers(svtme_ctx *c, PicBuf &pb, hipStream_t s); // `s` waits for the other lanes' readers
 // `pb`, written on `s` (its `ready` exists): the lanes of `lanes` wait for that before they read it
 svtme_status upload_publish(PicBuf &pb, hipStream_t s, uint32_t lanes);
-svtme_status alloc_pic(svtme_ctx *c, uint64_t pn, uint32_t W, uint32_t H, PicBuf **out, bool keep_chroma = false);
+svtme_status alloc_pic(svtme_ctx *c, uint64_t pn, uint32_t W, uint32_t H, PicBuf **out, bool keep_chroma = false,
+                       bool keep_hbd = false);
 svtme_status alloc_chroma(svtme_ctx *c, PicBuf &pb);
+svtme_status alloc_hbd(svtme_ctx *c, PicBuf &pb);
+// the padded 16-bit plane from w x h true samples on the device (dsrc may be the plane's own interior)
+svtme_status build_hbd(const PicBuf *pb, const uint16_t *dsrc, uint32_t src_stride, uint32_t w, uint32_t h,
+                       hipStream_t st);
 svtme_status build_pyramid(svtme_ctx *c, PicBuf *pb, const void *dsrc, uint32_t src_stride, uint32_t w, uint32_t h,
                            int ten_bit, hipStream_t st = nullptr);
 svtme_status build_chroma(const PicBuf *pb, int plane, const void *dsrc, uint32_t src_stride, uint32_t cw,

@@ -214,6 +214,17 @@ static inline void svtme_chroma_geometry(uint32_t W, uint32_t H, uint32_t *w, ui
     *rows   = *h + 2 * *top;
 }
 
+// geometry of the attached 16-bit luma plane (svtme_picture_attach_10bit) of an aligned W x H picture:
+// level 0's in samples (80 left, at least 88 right, 72 rows above and below, the logical padding
+// SVTME_PAD_FULL), two bytes a sample; `stride` is in bytes. A DevPlane describes it with `base` at
+// sample (0, 0), the stride in bytes and width, height and pad in samples.
+static inline void svtme_hbd_geometry(uint32_t W, uint32_t H, uint32_t *left, uint32_t *top, uint32_t *stride,
+                                      uint32_t *rows) {
+    *left = SVTME_DEV_FULL_LEFT, *top = SVTME_DEV_FULL_TOP;
+    *stride = svtme_round_up((W + SVTME_DEV_FULL_LEFT + 88) * 2, 64);
+    *rows   = H + 2 * *top;
+}
+
 // Arguments of the chroma stage of temporal filtering (svtme_tff.hip: k_tff_pred_uv, k_tff_norm_uv,
 // k_tff_norm_uv_pic), filled by the host. Plane 0 is Cb, 1 is Cr; every picture of a window has the
 // same chroma geometry, so the references are base pointers with one stride.
@@ -243,3 +254,5 @@ struct TffcArgs {
 #define SVTME_TFFC_WGT_BYTES 128    // chroma weights: `A.wgt[unit * 32 + ...]`, 32 dwords
 #define SVTME_TFFC_PLANE_SB_BYTES 1024 // one SB of one dense chroma plane: k_tff_norm_uv, `pl * A.sbs * 1024`
 // (the dense luma plane of k_tff_norm holds SVTME_TFF_TILE_BYTES per SB: whole 64 x 64 SBs)
+#define SVTME_TFFH_TILE_BYTES 8192  // 16-bit luma prediction: k_tffh_pred / k_tffh_norm, `A.tile + unit * 4096` samples
+// (svtme_tffh.hip shares the weight and error sections; its dense plane holds SVTME_TFFH_TILE_BYTES per SB)

@@ -151,4 +151,15 @@ hipError_t svtme_launch_tff_pic_yuv(const DevPlane *cen, const DevPlane *ref, ui
                                     uint32_t height, const svtme_tf_filter_controls *ctl,
                                     const svtme_tf_subpel_sb *d_sub, uint8_t *d_tile, uint32_t *d_wgt, uint32_t *d_e32,
                                     const DevPlane *dst, const TffcArgs *U, hipStream_t s);
+// svtme_tffh.hip: the 10-bit filter; its planes are 16-bit (svtme_hbd_geometry), src_stride in samples
+hipError_t svtme_prime_tffh(void);
+hipError_t svtme_launch_build_full16(const uint16_t *src, uint32_t src_stride, int w, int h, DevPlane dst, int left,
+                                     int top, int rows, hipStream_t s);
+hipError_t svtme_launch_tffh(const DevPlane *cen, const DevPlane *ref, uint32_t n, uint32_t width, uint32_t height,
+                             const svtme_tf_filter_controls *ctl, const svtme_tf_subpel_sb *d_sub, uint16_t *d_tile,
+                             uint32_t *d_wgt, uint32_t *d_e32, uint16_t *d_plane, hipStream_t s);
+hipError_t svtme_launch_tffh_pic(const DevPlane *cen, const DevPlane *ref, uint32_t n, uint32_t width, uint32_t height,
+                                 const svtme_tf_filter_controls *ctl, const svtme_tf_subpel_sb *d_sub, uint16_t *d_tile,
+                                 uint32_t *d_wgt, uint32_t *d_e32, const DevPlane *dst, const DevPlane *dst8,
+                                 hipStream_t s);
 }

@@ -72,6 +72,8 @@ static uint8_t *sweep_graves(svtme_ctx *c, size_t want) {
             give_free(c, g.bytes, g.mem);
         if (g.cmem) // the chroma attached to a released picture goes with it
             give_free(c, g.cbytes, g.cmem);
+        if (g.hmem) // the 16-bit plane likewise
+            give_free(c, g.hbytes, g.hmem);
         c->graves[i] = c->graves.back();
         c->graves.pop_back();
     }
@@ -156,13 +158,51 @@ svtme_status svtme_host::alloc_chroma(svtme_ctx *c, PicBuf &pb) {
     return SVTME_OK;
 }
 
-// allocate the three planes of a W x H picture in one buffer; chroma attached to an earlier picture
-// of the number is dropped unless the caller writes it too (svtme_tf_window_yuv)
+// bytes of the padded 16-bit plane of a W x H picture
+static size_t hbd_bytes(uint32_t W, uint32_t H) {
+    uint32_t left, top, stride, rows;
+    svtme_hbd_geometry(W, H, &left, &top, &stride, &rows);
+    return align256((size_t)stride * rows) + 256; // slack: the staging's aligned dword pairs end inside the row
+}
+
+// The picture's luma is about to be replaced: its 16-bit plane no longer belongs to it (drop_chroma's way)
+static void drop_hbd(svtme_ctx *c, PicBuf &pb) {
+    if (!pb.hmem)
+        return;
+    PicBuf g;
+    g.mem = pb.hmem, g.bytes = pb.hbytes;
+    for (int l = 0; l < SVTME_LANES; l++) g.used[l] = pb.used[l];
+    c->graves.push_back(g);
+    pb.hmem = nullptr, pb.hbytes = 0;
+    pb.hbd = DevPlane{};
+}
+
+// a 16-bit plane for a resident picture that has none (contents undefined until written)
+svtme_status svtme_host::alloc_hbd(svtme_ctx *c, PicBuf &pb) {
+    if (pb.hmem)
+        return SVTME_OK;
+    const size_t total = hbd_bytes(pb.W, pb.H);
+    svtme_status st    = pic_mem(c, total, &pb.hmem);
+    if (st)
+        return st;
+    pb.hbytes = total;
+    uint32_t left, top, stride, rows;
+    svtme_hbd_geometry(pb.W, pb.H, &left, &top, &stride, &rows);
+    pb.hbd = DevPlane{pb.hmem + (size_t)top * stride + (size_t)left * 2, (int32_t)stride, (int32_t)pb.W, (int32_t)pb.H,
+                      SVTME_PAD_FULL};
+    return SVTME_OK;
+}
+
+// allocate the three planes of a W x H picture in one buffer; chroma and the 16-bit plane attached to
+// an earlier picture of the number are dropped unless the caller writes them too (svtme_tf_window_yuv,
+// svtme_tf_window_10bit)
 svtme_status svtme_host::alloc_pic(svtme_ctx *c, uint64_t pn, uint32_t W, uint32_t H, PicBuf **out,
-                                   bool keep_chroma) {
+                                   bool keep_chroma, bool keep_hbd) {
     auto it = c->pics.find(pn);
     if (it != c->pics.end() && it->second.W == W && it->second.H == H && !keep_chroma)
         drop_chroma(c, it->second);
+    if (it != c->pics.end() && it->second.W == W && it->second.H == H && !keep_hbd)
+        drop_hbd(c, it->second);
     if (it != c->pics.end() && (it->second.W != W || it->second.H != H)) {
         // a new size: the old buffer goes to the graves (freed for reuse once its readers ran)
         c->graves.push_back(it->second);
@@ -513,9 +553,9 @@ extern "C" svtme_status svtme_picture_release(svtme_ctx *c, uint64_t pn) {
 
 // Copy a padded plane back in the reference's geometry, (h + 2 pad) rows of (w + 2 pad) bytes,
 // once every stream has run; a null dst asks for the geometry alone
-static svtme_status download_plane(svtme_ctx *c, const DevPlane &p, uint8_t *dst, uint32_t *stride, uint32_t *width,
-                                   uint32_t *height, uint32_t *pad) {
-    const uint32_t S = (uint32_t)(p.width + 2 * p.pad);
+static svtme_status download_plane(svtme_ctx *c, const DevPlane &p, void *dst, uint32_t *stride, uint32_t *width,
+                                   uint32_t *height, uint32_t *pad, uint32_t bpp = 1) {
+    const uint32_t S = (uint32_t)(p.width + 2 * p.pad); // samples, bpp bytes each
     if (stride)
         *stride = S;
     if (width)
@@ -530,8 +570,8 @@ static svtme_status download_plane(svtme_ctx *c, const DevPlane &p, uint8_t *dst
     svtme_status qs = quiesce(c);
     if (qs)
         return qs;
-    HIP_TRY(hipMemcpy2D(dst, S, p.base - (ptrdiff_t)p.pad * p.stride - p.pad, (size_t)p.stride, S,
-                        (size_t)(p.height + 2 * p.pad), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy2D(dst, (size_t)S * bpp, p.base - (ptrdiff_t)p.pad * p.stride - (ptrdiff_t)p.pad * bpp,
+                        (size_t)p.stride, (size_t)S * bpp, (size_t)(p.height + 2 * p.pad), hipMemcpyDeviceToHost));
     return SVTME_OK;
 }
 
@@ -605,4 +645,56 @@ extern "C" svtme_status svtme_picture_download_chroma(svtme_ctx *c, uint64_t pn,
         return fail(SVTME_ERR_BAD_PARAMETER, "svtme_picture_download_chroma: picture %llu %s", (unsigned long long)pn,
                     !pb ? "is not resident" : "has no chroma");
     return download_plane(c, pb->chroma[plane - 1], dst, stride, width, height, pad);
+}
+
+// ---- the full-precision luma of a 10-bit picture ----
+svtme_status svtme_host::build_hbd(const PicBuf *pb, const uint16_t *dsrc, uint32_t src_stride, uint32_t w, uint32_t h,
+                                   hipStream_t st) {
+    uint32_t left, top, stride, rows;
+    svtme_hbd_geometry(pb->W, pb->H, &left, &top, &stride, &rows);
+    HIP_TRY(svtme_launch_build_full16(dsrc, src_stride, (int)w, (int)h, pb->hbd, (int)left, (int)top, (int)rows, st));
+    return SVTME_OK;
+}
+
+extern "C" svtme_status svtme_picture_attach_10bit(svtme_ctx *c, uint64_t pn, const uint16_t *y, uint32_t stride,
+                                                   uint32_t w, uint32_t h) {
+    if (!c || !y || w == 0 || h == 0)
+        return fail(SVTME_ERR_BAD_PARAMETER, "svtme_picture_attach_10bit: null ctx or y, or a %ux%u picture", w, h);
+    if (stride < w)
+        return fail(SVTME_ERR_BAD_PARAMETER, "svtme_picture_attach_10bit: stride %u under the width %u", stride, w);
+    std::lock_guard<std::mutex> lk(c->mu);
+    PicBuf *pbp = find_pic(c, pn);
+    if (!pbp)
+        return fail(SVTME_ERR_BAD_PARAMETER, "svtme_picture_attach_10bit: picture %llu is not resident",
+                    (unsigned long long)pn);
+    PicBuf &pb = *pbp;
+    if (pb.W != svtme_align8_u(w) || pb.H != svtme_align8_u(h))
+        return fail(SVTME_ERR_BAD_PARAMETER, "svtme_picture_attach_10bit: picture %llu is %ux%u, the plane %ux%u",
+                    (unsigned long long)pn, pb.W, pb.H, w, h);
+    HIP_TRY(hipSetDevice(c->device));
+    svtme_status st;
+    if ((st = alloc_hbd(c, pb)) || (st = ensure_buf(&c->staging, &c->staging_cap, (size_t)w * h * 2)))
+        return st;
+    // (the staging plane is reused in stream order, as upload_sync does)
+    HIP_TRY(hipMemcpy2DAsync(c->staging, (size_t)w * 2, y, (size_t)stride * 2, (size_t)w * 2, h, hipMemcpyHostToDevice,
+                             c->stream));
+    // queued jobs of the other lanes may still read the old plane (lane 0's run before by stream order)
+    if ((st = after_readers(c, pb, c->stream)) || (st = build_hbd(&pb, (const uint16_t *)c->staging, w, w, h, c->stream)))
+        return st;
+    // later jobs of the other lanes wait for the plane: the stream is drained before the call returns
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return SVTME_OK;
+}
+
+// Copy the 16-bit plane back in the shape of svtme_picture_download; the stride is in samples
+extern "C" svtme_status svtme_picture_download_10bit(svtme_ctx *c, uint64_t pn, uint16_t *dst, uint32_t *stride,
+                                                     uint32_t *width, uint32_t *height, uint32_t *pad) {
+    if (!c)
+        return fail(SVTME_ERR_BAD_PARAMETER, "svtme_picture_download_10bit: null ctx");
+    std::lock_guard<std::mutex> lk(c->mu);
+    const PicBuf *pb = find_pic(c, pn);
+    if (!pb || !pb->hmem)
+        return fail(SVTME_ERR_BAD_PARAMETER, "svtme_picture_download_10bit: picture %llu %s", (unsigned long long)pn,
+                    !pb ? "is not resident" : "has no 10-bit plane");
+    return download_plane(c, pb->hbd, dst, stride, width, height, pad, 2);
 }

@@ -1,5 +1,5 @@
 // svtme_windows.cpp — the calls over a window of resident pictures, all on lane 0: the dynamic-GOP
-// detector (svtme_dg.hip) and temporal filtering's stages (svtme_tfsp.hip, svtme_tff.hip), alone
+// detector (svtme_dg.hip) and temporal filtering's stages (svtme_tfsp.hip, svtme_tff.hip, svtme_tffh.hip), alone
 // and as one window resident to resident. Each holds the context lock from its first launch to
 // its last copy, as svtme_submit_picture does: the device outputs are the context's, and a
 // release / invalidate of a picture from another thread waits for the lock.
@@ -66,9 +66,10 @@ extern "C" svtme_status svtme_dg_detect(svtme_ctx *c, const svtme_dg_pair *pairs
 
 // ---- what the temporal-filter calls share ----
 // The resident pictures pn[0..count) of a window, each W x H (8-aligned) and, where the call
-// filters chroma, with chroma attached. The first picture that fails decides the message.
+// filters chroma, with chroma attached, where it filters 10-bit luma, with the 16-bit plane
+// attached. The first picture that fails decides the message.
 static svtme_status resident_pics(svtme_ctx *c, const char *fn, const uint64_t *pn, uint32_t count, uint32_t W,
-                                  uint32_t H, bool chroma, PicBuf **pb) {
+                                  uint32_t H, bool chroma, PicBuf **pb, bool hbd = false) {
     for (uint32_t k = 0; k < count; k++) {
         if (!(pb[k] = find_pic(c, pn[k])))
             return fail(SVTME_ERR_BAD_PARAMETER, "%s: picture %llu is not resident", fn, (unsigned long long)pn[k]);
@@ -77,6 +78,8 @@ static svtme_status resident_pics(svtme_ctx *c, const char *fn, const uint64_t *
                         (unsigned long long)pn[k], pb[k]->W, pb[k]->H, W, H);
         if (chroma && !pb[k]->cmem)
             return fail(SVTME_ERR_BAD_PARAMETER, "%s: picture %llu has no chroma", fn, (unsigned long long)pn[k]);
+        if (hbd && !pb[k]->hmem)
+            return fail(SVTME_ERR_BAD_PARAMETER, "%s: picture %llu has no 10-bit plane", fn, (unsigned long long)pn[k]);
     }
     return SVTME_OK;
 }
@@ -116,6 +119,7 @@ static svtme_status tff_controls_check(const char *fn, const char *what, const s
 //   results of the sub-pel stage | luma tiles | weights | errors | (dense) the luma plane, whole SBs |
 //   (chroma) Cb and Cr tiles | weights | (chroma, dense) the two planes, whole SBs
 // (704 bytes a result, multiples of 16 per unit or SB elsewhere: the sections stay 16-byte aligned).
+// The 10-bit calls (hbd) hold 16-bit luma tiles and a 16-bit dense plane in the same places.
 // The stage calls copy dense planes out; the window call writes the result picture and has none.
 struct TfScratch {
     svtme_tf_subpel_sb *sub;
@@ -125,7 +129,8 @@ struct TfScratch {
     uint32_t *cwgt;
     size_t sub_bytes, e32_bytes, cplane_bytes;
 };
-static svtme_status tf_scratch(svtme_ctx *c, uint32_t n, uint32_t sbs, bool dense, bool chroma, TfScratch *S) {
+static svtme_status tf_scratch(svtme_ctx *c, uint32_t n, uint32_t sbs, bool dense, bool chroma, TfScratch *S,
+                               bool hbd = false) {
     const size_t units = (size_t)n * sbs;
     S->sub_bytes    = sizeof(svtme_tf_subpel_sb) * units;
     S->e32_bytes    = SVTME_TFF_E32_BYTES * units;
@@ -136,9 +141,10 @@ static svtme_status tf_scratch(svtme_ctx *c, uint32_t n, uint32_t sbs, bool dens
         end += present ? bytes : 0;
         return at;
     };
-    const size_t o_sub = take(true, S->sub_bytes), o_tile = take(true, SVTME_TFF_TILE_BYTES * units),
+    const size_t tile_bytes = hbd ? SVTME_TFFH_TILE_BYTES : SVTME_TFF_TILE_BYTES;
+    const size_t o_sub = take(true, S->sub_bytes), o_tile = take(true, tile_bytes * units),
                  o_wgt = take(true, SVTME_TFF_WGT_BYTES * units), o_e32 = take(true, S->e32_bytes),
-                 o_plane = take(dense, (size_t)SVTME_TFF_TILE_BYTES * sbs),
+                 o_plane = take(dense, tile_bytes * sbs),
                  o_ctile = take(chroma, SVTME_TFFC_TILE_BYTES * units),
                  o_cwgt = take(chroma, SVTME_TFFC_WGT_BYTES * units),
                  o_cplane = take(chroma && dense, 2 * S->cplane_bytes);
@@ -157,6 +163,12 @@ struct TfChroma {
     uint32_t decay[2];
     uint8_t *out[2]; // Cb, Cr; either may be NULL
     uint32_t stride[2];
+};
+
+// the 10-bit side of svtme_tf_filter_10bit / svtme_tf_window_10bit: the host copy of the 16-bit plane
+struct TfHbd {
+    uint16_t *out; // the filter call: required; the window call: may be NULL
+    uint32_t stride; // samples
 };
 
 // checked before any GPU work: a stride under the chroma width
@@ -237,8 +249,10 @@ extern "C" svtme_status svtme_tf_subpel(svtme_ctx *c, uint64_t centre_picture_nu
 }
 
 // ---- Temporal filtering's prediction and weighting (svtme_tff.hip) ----
-// svtme_tf_filter (uv NULL) and svtme_tf_filter_yuv
-static svtme_status tf_filter_impl(const char *fn, const TfChroma *uv, svtme_ctx *c, uint64_t centre_picture_number,
+// svtme_tf_filter (uv and hb NULL), svtme_tf_filter_yuv (uv) and svtme_tf_filter_10bit (hb: `out` and
+// `out_stride` are hb's, the stride in samples)
+static svtme_status tf_filter_impl(const char *fn, const TfChroma *uv, const TfHbd *hb, svtme_ctx *c,
+                                   uint64_t centre_picture_number,
                                    const uint64_t *ref_picture_numbers, uint32_t n, uint32_t width, uint32_t height,
                                    const svtme_tf_filter_controls *ctl, const svtme_tf_subpel_sb *subpel, uint8_t *out,
                                    uint32_t out_stride, uint32_t *err32_out) {
@@ -264,17 +278,22 @@ static svtme_status tf_filter_impl(const char *fn, const TfChroma *uv, svtme_ctx
     memcpy(pn + 1, ref_picture_numbers, n * sizeof(uint64_t));
     std::lock_guard<std::mutex> lk(c->mu);
     PicBuf *pb[SVTME_MAX_BATCH_JOBS + 1];
-    if ((st = resident_pics(c, fn, pn, n + 1, W, H, uv != nullptr, pb)))
+    if ((st = resident_pics(c, fn, pn, n + 1, W, H, uv != nullptr, pb, hb != nullptr)))
         return st;
     HIP_TRY(hipSetDevice(c->device));
     TfScratch S;
     DevPlane ref[SVTME_MAX_BATCH_JOBS];
-    if ((st = tf_scratch(c, n, sbs, true, uv != nullptr, &S)) || (st = join_window(c, pb, n, ref)))
+    if ((st = tf_scratch(c, n, sbs, true, uv != nullptr, &S, hb != nullptr)) || (st = join_window(c, pb, n, ref)))
         return st;
     Lane &L              = c->lanes[0];
     const size_t pstride = (size_t)((W + 63) / 64) * 64; // of the dense luma plane; the chroma planes' is half
     HIP_TRY(hipMemcpyAsync(S.sub, subpel, S.sub_bytes, hipMemcpyHostToDevice, L.s));
-    HIP_TRY(svtme_launch_tff(&pb[0]->pyr.lv[0], ref, n, W, H, ctl, S.sub, S.tile, S.wgt, S.e32, S.plane, L.s));
+    if (hb) {
+        for (uint32_t k = 0; k < n; k++) ref[k] = pb[k + 1]->hbd;
+        HIP_TRY(svtme_launch_tffh(&pb[0]->hbd, ref, n, W, H, ctl, S.sub, (uint16_t *)S.tile, S.wgt, S.e32,
+                                  (uint16_t *)S.plane, L.s));
+    } else
+        HIP_TRY(svtme_launch_tff(&pb[0]->pyr.lv[0], ref, n, W, H, ctl, S.sub, S.tile, S.wgt, S.e32, S.plane, L.s));
     if (uv) {
         TffcArgs U{};
         tffc_fill(U, pb, n, W, H, ctl, uv, S);
@@ -284,7 +303,9 @@ static svtme_status tf_filter_impl(const char *fn, const TfChroma *uv, svtme_ctx
     if ((st = submission_done(L, &done)))
         return st;
     mark_read(pb, n + 1, 0, done);
-    HIP_TRY(hipMemcpy2DAsync(out, out_stride, S.plane, pstride, width, height, hipMemcpyDeviceToHost, L.s));
+    const size_t bpp = hb ? 2 : 1;
+    HIP_TRY(hipMemcpy2DAsync(out, out_stride * bpp, S.plane, pstride * bpp, width * bpp, height, hipMemcpyDeviceToHost,
+                             L.s));
     if (err32_out)
         HIP_TRY(hipMemcpyAsync(err32_out, S.e32, S.e32_bytes, hipMemcpyDeviceToHost, L.s));
     for (int p = 0; uv && p < 2; p++)
@@ -300,7 +321,7 @@ extern "C" svtme_status svtme_tf_filter(svtme_ctx *c, uint64_t centre_picture_nu
                                         uint32_t height, const svtme_tf_filter_controls *ctl,
                                         const svtme_tf_subpel_sb *subpel, uint8_t *out, uint32_t out_stride,
                                         uint32_t *err32_out) {
-    return tf_filter_impl("svtme_tf_filter", nullptr, c, centre_picture_number, ref_picture_numbers, n, width, height,
+    return tf_filter_impl("svtme_tf_filter", nullptr, nullptr, c, centre_picture_number, ref_picture_numbers, n, width, height,
                           ctl, subpel, out, out_stride, err32_out);
 }
 
@@ -313,8 +334,18 @@ extern "C" svtme_status svtme_tf_filter_yuv(svtme_ctx *c, uint64_t centre_pictur
     const TfChroma uv = {{ctl->tf_decay_factor_cb_fp16, ctl->tf_decay_factor_cr_fp16},
                          {out->cb, out->cr},
                          {out->cb_stride, out->cr_stride}};
-    return tf_filter_impl("svtme_tf_filter_yuv", &uv, c, centre_picture_number, ref_picture_numbers, n, width, height,
+    return tf_filter_impl("svtme_tf_filter_yuv", &uv, nullptr, c, centre_picture_number, ref_picture_numbers, n, width, height,
                           &ctl->luma, subpel, out->y, out->y_stride, out->err32);
+}
+
+extern "C" svtme_status svtme_tf_filter_10bit(svtme_ctx *c, uint64_t centre_picture_number,
+                                              const uint64_t *ref_picture_numbers, uint32_t n, uint32_t width,
+                                              uint32_t height, const svtme_tf_filter_controls *ctl,
+                                              const svtme_tf_subpel_sb *subpel, uint16_t *out, uint32_t out_stride,
+                                              uint32_t *err32_out) {
+    const TfHbd hb = {out, out_stride};
+    return tf_filter_impl("svtme_tf_filter_10bit", nullptr, &hb, c, centre_picture_number, ref_picture_numbers, n, width,
+                          height, ctl, subpel, (uint8_t *)out, out_stride, err32_out);
 }
 
 // ----------------------------------------------------------------------------
@@ -322,8 +353,10 @@ extern "C" svtme_status svtme_tf_filter_yuv(svtme_ctx *c, uint64_t centre_pictur
 // k_tff_pred and the normalisation into the result picture, chained by lane 0's
 // stream through the two stages' scratch.
 // ----------------------------------------------------------------------------
-// svtme_tf_window (uv NULL) and svtme_tf_window_yuv
-static svtme_status tf_window_impl(const char *fn, const TfChroma *uv, svtme_ctx *c, const svtme_job *jobs, uint32_t n,
+// svtme_tf_window (uv and hb NULL), svtme_tf_window_yuv (uv) and svtme_tf_window_10bit (hb: the TF-ME
+// batch and k_tfsp on the MSB planes as ever, then svtme_tffh.hip on the 16-bit planes)
+static svtme_status tf_window_impl(const char *fn, const TfChroma *uv, const TfHbd *hb, svtme_ctx *c,
+                                   const svtme_job *jobs, uint32_t n,
                                    uint32_t src_width, uint32_t src_height, const svtme_tf_subpel_controls *sp_ctl,
                                    const svtme_tf_filter_controls *f_ctl, uint64_t out_pn,
                                    const svtme_tf_window_out *out) {
@@ -358,6 +391,8 @@ static svtme_status tf_window_impl(const char *fn, const TfChroma *uv, svtme_ctx
     if (out && out->plane && out->plane_stride < src_width)
         return fail(SVTME_ERR_BAD_PARAMETER, "%s: plane_stride %u under the width %u", fn, out->plane_stride,
                     src_width);
+    if (hb && hb->out && hb->stride < src_width)
+        return fail(SVTME_ERR_BAD_PARAMETER, "%s: plane16_stride %u under the width %u", fn, hb->stride, src_width);
     svtme_status st;
     if ((uv && (st = chroma_strides_ok(fn, uv, src_width))) || (st = tfsp_controls_check(fn, "sub-pel controls", sp_ctl)) ||
         (st = tff_controls_check(fn, "filter controls", f_ctl)))
@@ -374,13 +409,13 @@ static svtme_status tf_window_impl(const char *fn, const TfChroma *uv, svtme_ctx
     // the batch and the result picture's allocation: std::map keeps its other nodes where they
     // are, and the result picture, where it is the centre, has the centre's size and stays too.
     PicBuf *pb[SVTME_MAX_BATCH_JOBS + 1];
-    if ((st = resident_pics(c, fn, pn, n + 1, W, H, uv != nullptr, pb)))
+    if ((st = resident_pics(c, fn, pn, n + 1, W, H, uv != nullptr, pb, hb != nullptr)))
         return st;
     HIP_TRY(hipSetDevice(c->device));
     // the sub-pel scratch holds the records (its results go to the filter's scratch)
     const size_t rec_bytes = sizeof(svtme_ref_record) * (size_t)n * sbs;
     TfScratch S;
-    if ((st = ensure_buf(&c->d_tfsp, &c->tfsp_cap, rec_bytes)) || (st = tf_scratch(c, n, sbs, false, uv != nullptr, &S)))
+    if ((st = ensure_buf(&c->d_tfsp, &c->tfsp_cap, rec_bytes)) || (st = tf_scratch(c, n, sbs, false, uv != nullptr, &S, hb != nullptr)))
         return st;
     svtme_ref_record *d_rec = (svtme_ref_record *)c->d_tfsp;
     // the TF-ME jobs: one batch, job k's records (R = 1) at d_rec + k x SBs, the array k_tfsp reads
@@ -390,7 +425,8 @@ static svtme_status tf_window_impl(const char *fn, const TfChroma *uv, svtme_ctx
         return st;
     // the result picture (a new number: a buffer of the pool)
     PicBuf *po;
-    if ((st = alloc_pic(c, out_pn, W, H, &po, uv != nullptr)) || (uv && (st = alloc_chroma(c, *po))))
+    if ((st = alloc_pic(c, out_pn, W, H, &po, uv != nullptr, hb != nullptr)) || (uv && (st = alloc_chroma(c, *po))) ||
+        (hb && (st = alloc_hbd(c, *po))))
         return st;
     Lane &L = c->lanes[0];
     DevPlane ref[SVTME_MAX_BATCH_JOBS];
@@ -406,6 +442,14 @@ static svtme_status tf_window_impl(const char *fn, const TfChroma *uv, svtme_ctx
         U.dst[0] = po->chroma[0], U.dst[1] = po->chroma[1];
         HIP_TRY(svtme_launch_tff_pic_yuv(&pb[0]->pyr.lv[0], ref, n, W, H, f_ctl, S.sub, S.tile, S.wgt, S.e32,
                                          &po->pyr.lv[0], &U, L.s));
+    } else if (hb) {
+        DevPlane ref16[SVTME_MAX_BATCH_JOBS];
+        for (uint32_t k = 0; k < n; k++) ref16[k] = pb[k + 1]->hbd;
+        HIP_TRY(svtme_launch_tffh_pic(&pb[0]->hbd, ref16, n, W, H, f_ctl, S.sub, (uint16_t *)S.tile, S.wgt, S.e32,
+                                      &po->hbd, &po->pyr.lv[0], L.s));
+        // the 16-bit plane beyond the true size and its margins, from its own interior
+        if ((st = build_hbd(po, (const uint16_t *)po->hbd.base, (uint32_t)po->hbd.stride / 2, src_width, src_height, L.s)))
+            return st;
     } else
         HIP_TRY(svtme_launch_tff_pic(&pb[0]->pyr.lv[0], ref, n, W, H, f_ctl, S.sub, S.tile, S.wgt, S.e32,
                                      &po->pyr.lv[0], L.s));
@@ -428,7 +472,8 @@ static svtme_status tf_window_impl(const char *fn, const TfChroma *uv, svtme_ctx
     if ((st = upload_publish(*po, L.s, kAllLanes & ~1u)))
         return st;
     const bool want_uv = uv && (uv->out[0] || uv->out[1]);
-    if (!want_uv && (!out || (!out->plane && !out->records && !out->subpel && !out->err32)))
+    const bool want_16 = hb && hb->out;
+    if (!want_uv && !want_16 && (!out || (!out->plane && !out->records && !out->subpel && !out->err32)))
         return SVTME_OK;
     if (out && out->records)
         HIP_TRY(hipMemcpyAsync(out->records, d_rec, rec_bytes, hipMemcpyDeviceToHost, L.s));
@@ -439,6 +484,9 @@ static svtme_status tf_window_impl(const char *fn, const TfChroma *uv, svtme_ctx
     if (out && out->plane)
         HIP_TRY(hipMemcpy2DAsync(out->plane, out->plane_stride, po->pyr.lv[0].base, (size_t)po->pyr.lv[0].stride,
                                  src_width, src_height, hipMemcpyDeviceToHost, L.s));
+    if (want_16)
+        HIP_TRY(hipMemcpy2DAsync(hb->out, (size_t)hb->stride * 2, po->hbd.base, (size_t)po->hbd.stride,
+                                 (size_t)src_width * 2, src_height, hipMemcpyDeviceToHost, L.s));
     for (int p = 0; want_uv && p < 2; p++)
         if (uv->out[p])
             HIP_TRY(hipMemcpy2DAsync(uv->out[p], uv->stride[p], po->chroma[p].base, (size_t)po->chroma[p].stride,
@@ -451,7 +499,7 @@ extern "C" svtme_status svtme_tf_window(svtme_ctx *c, const svtme_job *jobs, uin
                                         uint32_t src_height, const svtme_tf_subpel_controls *sp_ctl,
                                         const svtme_tf_filter_controls *f_ctl, uint64_t out_pn,
                                         const svtme_tf_window_out *out) {
-    return tf_window_impl("svtme_tf_window", nullptr, c, jobs, n, src_width, src_height, sp_ctl, f_ctl, out_pn, out);
+    return tf_window_impl("svtme_tf_window", nullptr, nullptr, c, jobs, n, src_width, src_height, sp_ctl, f_ctl, out_pn, out);
 }
 
 extern "C" svtme_status svtme_tf_window_yuv(svtme_ctx *c, const svtme_job *jobs, uint32_t n, uint32_t src_width,
@@ -463,6 +511,15 @@ extern "C" svtme_status svtme_tf_window_yuv(svtme_ctx *c, const svtme_job *jobs,
     const TfChroma uv = {{f_ctl->tf_decay_factor_cb_fp16, f_ctl->tf_decay_factor_cr_fp16},
                          {out_uv ? out_uv->cb : nullptr, out_uv ? out_uv->cr : nullptr},
                          {out_uv ? out_uv->cb_stride : 0, out_uv ? out_uv->cr_stride : 0}};
-    return tf_window_impl("svtme_tf_window_yuv", &uv, c, jobs, n, src_width, src_height, sp_ctl, &f_ctl->luma, out_pn,
+    return tf_window_impl("svtme_tf_window_yuv", &uv, nullptr, c, jobs, n, src_width, src_height, sp_ctl, &f_ctl->luma, out_pn,
+                          out);
+}
+
+extern "C" svtme_status svtme_tf_window_10bit(svtme_ctx *c, const svtme_job *jobs, uint32_t n, uint32_t src_width,
+                                              uint32_t src_height, const svtme_tf_subpel_controls *sp_ctl,
+                                              const svtme_tf_filter_controls *f_ctl, uint64_t out_pn,
+                                              const svtme_tf_window_out *out, uint16_t *plane16, uint32_t plane16_stride) {
+    const TfHbd hb = {plane16, plane16_stride};
+    return tf_window_impl("svtme_tf_window_10bit", nullptr, &hb, c, jobs, n, src_width, src_height, sp_ctl, f_ctl, out_pn,
                           out);
 }

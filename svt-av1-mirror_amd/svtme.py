@@ -781,6 +781,17 @@ def _job_api_protos(lib):
                                                         C.POINTER(TfSubpelControls), C.POINTER(TfFilterYuvControls),
                                                         C.c_uint64, C.POINTER(TfWindowOut), C.POINTER(TfWindowYuvOut)])
         _proto(lib, "svtme_tf_window_yuv", "restype", C.c_int32)
+        _proto(lib, "svtme_picture_attach_10bit", "argtypes", [vp, C.c_uint64, vp, C.c_uint32, C.c_uint32, C.c_uint32])
+        _proto(lib, "svtme_picture_attach_10bit", "restype", C.c_int32)
+        _proto(lib, "svtme_picture_download_10bit", "argtypes", [vp, C.c_uint64, vp] + [C.POINTER(C.c_uint32)] * 4)
+        _proto(lib, "svtme_picture_download_10bit", "restype", C.c_int32)
+        _proto(lib, "svtme_tf_filter_10bit", "argtypes", [vp, C.c_uint64, C.POINTER(C.c_uint64), C.c_uint32, C.c_uint32,
+                                                          C.c_uint32, C.POINTER(TfFilterControls), vp, vp, C.c_uint32, vp])
+        _proto(lib, "svtme_tf_filter_10bit", "restype", C.c_int32)
+        _proto(lib, "svtme_tf_window_10bit", "argtypes", [vp, C.POINTER(Job), C.c_uint32, C.c_uint32, C.c_uint32,
+                                                          C.POINTER(TfSubpelControls), C.POINTER(TfFilterControls),
+                                                          C.c_uint64, C.POINTER(TfWindowOut), vp, C.c_uint32])
+        _proto(lib, "svtme_tf_window_10bit", "restype", C.c_int32)
         lib._svtme_protos = True
     return lib
 
@@ -1166,6 +1177,75 @@ class GpuME:
                                                  C.byref(out) if res else None, C.byref(out_uv) if uv else None),
                     "svtme_tf_window_yuv")
         return dict(res, **uv)
+
+    def attach_10bit(self, picture_number: int, y: np.ndarray):
+        """svtme_picture_attach_10bit: attach the full-precision luma (uint16, 0..1023) to the resident
+        picture, normally one uploaded from the same array (upload keeps the MSB plane only)."""
+        y = np.ascontiguousarray(y, np.uint16)
+        h, w = y.shape
+        self._check(self.lib.svtme_picture_attach_10bit(self.ctx, picture_number, y.ctypes.data, w, w, h),
+                    "svtme_picture_attach_10bit")
+
+    def download_10bit(self, picture_number: int) -> np.ndarray:
+        """svtme_picture_download_10bit: the 16-bit plane with its margins, (H + 144, W + 144) u16."""
+        stride, w, h, pad = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32()
+        args = (C.byref(stride), C.byref(w), C.byref(h), C.byref(pad))
+        self._check(self.lib.svtme_picture_download_10bit(self.ctx, picture_number, None, *args),
+                    "svtme_picture_download_10bit")
+        out = np.empty((h.value + 2 * pad.value, stride.value), np.uint16)
+        self._check(self.lib.svtme_picture_download_10bit(self.ctx, picture_number, out.ctypes.data, *args),
+                    "svtme_picture_download_10bit")
+        return out
+
+    def tf_filter_10bit(self, centre: int, refs, width: int, height: int, controls: TfFilterControls,
+                        subpel: np.ndarray, with_err32: bool = True, out_stride: int = None):
+        """svtme_tf_filter_10bit: tf_filter on the attached 16-bit planes, `subpel` from tf_subpel on the
+        MSB planes -> (plane [height, width] u16, err32 [len(refs), SBs, 4] u32 or None). With out_stride
+        (samples) the plane is a view of rows that far apart."""
+        n = len(refs)
+        sbs = sb_total(align8(width), align8(height))
+        subpel = np.ascontiguousarray(subpel, TF_SUBPEL_SB_DTYPE)
+        if subpel.size != n * sbs:
+            raise ValueError(f"{subpel.size} sub-pel results for {n} references x {sbs} SBs")
+        arr = (C.c_uint64 * max(n, 1))(*[int(r) for r in refs])
+        stride = width if out_stride is None else out_stride
+        buf = np.zeros((height, stride), np.uint16)
+        err32 = np.zeros((n, sbs, 4), np.uint32) if with_err32 else None
+        self._check(self.lib.svtme_tf_filter_10bit(self.ctx, int(centre), arr, n, width, height, C.byref(controls),
+                                                   subpel.ctypes.data, buf.ctypes.data, stride,
+                                                   err32.ctypes.data if with_err32 else None), "svtme_tf_filter_10bit")
+        return buf[:, :width], err32
+
+    def tf_window_10bit(self, jobs, src_w: int, src_h: int, subpel_controls: TfSubpelControls,
+                        filter_controls: TfFilterControls, out_pn: int,
+                        want=("plane", "records", "subpel", "err32", "plane16")):
+        """svtme_tf_window_10bit: tf_window for pictures with an attached 16-bit plane; the result picture
+        `out_pn` gets the filtered 16-bit plane and its MSB pyramid. -> {name: array} of the outputs
+        named in `want`: tf_window's (plane: the MSB plane) and plane16 [src_h, src_w] u16."""
+        unknown = set(want) - {"plane", "records", "subpel", "err32", "plane16"}
+        if unknown:
+            raise ValueError(f"unknown outputs {sorted(unknown)}")
+        n = len(jobs)
+        arr = (Job * max(n, 1))(*jobs)
+        sbs = sb_total(align8(src_w), align8(src_h))
+        res = {}
+        if "plane" in want:
+            res["plane"] = np.zeros((src_h, src_w), np.uint8)
+        if "records" in want:
+            res["records"] = np.zeros((n, sbs), REF_RECORD_DTYPE)
+        if "subpel" in want:
+            res["subpel"] = np.zeros((n, sbs), TF_SUBPEL_SB_DTYPE)
+        if "err32" in want:
+            res["err32"] = np.zeros((n, sbs, 4), np.uint32)
+        p16 = np.zeros((src_h, src_w), np.uint16) if "plane16" in want else None
+        out = TfWindowOut(plane_stride=src_w, **{k: v.ctypes.data for k, v in res.items()})
+        self._check(self.lib.svtme_tf_window_10bit(self.ctx, arr, n, src_w, src_h, C.byref(subpel_controls),
+                                                   C.byref(filter_controls), int(out_pn), C.byref(out) if res else None,
+                                                   p16.ctypes.data if p16 is not None else None, src_w),
+                    "svtme_tf_window_10bit")
+        if p16 is not None:
+            res["plane16"] = p16
+        return res
 
     def device_records(self):
         n = C.c_uint64()
