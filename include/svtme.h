@@ -797,8 +797,8 @@ svtme_status svtme_tf_window_yuv(svtme_ctx *ctx, const svtme_job *jobs, uint32_t
  * 8-bit function with the window SSE >> 4, the 16x16 block error >> 4 and the
  * 32x32 block error >> 6 instead of >> 2), the accumulation and the normalisation
  * into 16-bit samples. Luma, 10 bit, use_zz_based_filter == 0, use_8bit_subpel ==
- * 1. Not served: 10-bit chroma, the high-bit-depth sub-pel search (use_8bit_subpel
- * == 0), the zz filter, 12 bit.
+ * 1; chroma beside it in the section after this one. Not served: the
+ * high-bit-depth sub-pel search (use_8bit_subpel == 0), the zz filter, 12 bit.
  * ------------------------------------------------------------------------- */
 /* Attach the full-precision luma (16-bit samples, values 0..1023, rows `stride`
  * SAMPLES apart) to a picture that is already resident, normally one uploaded with
@@ -809,7 +809,7 @@ svtme_status svtme_tf_window_yuv(svtme_ctx *ctx, const svtme_job *jobs, uint32_t
  * of the reference's padded 8-bit and 2-bit planes. Synchronous, ordered after
  * queued readers of the picture; released with the picture; any later luma upload,
  * svtme_picture_invalidate, svtme_tf_window or svtme_tf_window_yuv result under the
- * same number drops it. The 8-bit calls and the yuv calls never read it. Samples
+ * same number drops it. The 8-bit calls and the 8-bit yuv calls never read it. Samples
  * above 1023 are the caller's error: the results of the 10-bit calls are then
  * unspecified, but no read or write leaves the buffers. Returns
  * SVTME_ERR_BAD_PARAMETER before any GPU work for a NULL ctx / y, a zero size,
@@ -842,7 +842,7 @@ svtme_status svtme_tf_filter_10bit(svtme_ctx *ctx, uint64_t centre_picture_numbe
  * writes as the 8-bit plane) with its re-pad, margins and levels 1 and 2 made as
  * svtme_tf_window makes them: the picture is what svtme_picture_upload_10bit plus
  * svtme_picture_attach_10bit of the filtered plane leave. Chroma attached to the
- * result's number is dropped. out->plane receives the MSB plane; plane16 (NULL or
+ * result's number, 8-bit or 16-bit, is dropped. out->plane receives the MSB plane; plane16 (NULL or
  * rows plane16_stride SAMPLES apart, >= src_width) the 16-bit plane. In place, a
  * fresh number, the ordering guarantees, the asynchronous return when no host copy
  * is asked for and the refusals are svtme_tf_window's; refused too, before any GPU
@@ -852,6 +852,106 @@ svtme_status svtme_tf_window_10bit(svtme_ctx *ctx, const svtme_job *jobs, uint32
                                    uint32_t src_height, const svtme_tf_subpel_controls *subpel_controls,
                                    const svtme_tf_filter_controls *filter_controls, uint64_t out_picture_number,
                                    const svtme_tf_window_out *out, uint16_t *plane16, uint32_t plane16_stride);
+
+/* ---------------------------------------------------------------------------
+ * Temporal filtering of 10-bit pictures with chroma (is_highbd and tf_chroma: every
+ * level of tf_controls from 1 to 7 sets chroma_lvl 1 for at least one picture type,
+ * so presets M0 to M7 filter Cb and Cr beside luma on the packed 16-bit pictures).
+ * 10 bit, 4:2:0, use_zz_based_filter == 0, use_8bit_subpel == 1. The chroma stage is
+ * svtme_tf_filter_yuv's on 16-bit samples: the luma blocks and MVs, the chroma clamp,
+ * svt_highbd_inter_predictor at bd 10 with MULTITAP_SHARP at the chroma size
+ * (sub_pel_filters_4 for the 4x4 blocks), and the weights of
+ * svt_av1_apply_temporal_filter_planewise_medium_hbd_partial_c with is_chroma 1: the
+ * 8x8 quarter's SSE >> 4, times 4, blended 5 : 1 with the luma window error (the 16x16
+ * SSE >> 4) of the same quarter, the luma block errors >> 4 (split) or >> 6, the
+ * plane's own decay factor. With the 8-bit calls, the yuv calls and the 10-bit luma
+ * calls this completes {8, 10 bit} x {luma, yuv}. Not served: use_8bit_subpel == 0,
+ * the zz filter, 12 bit.
+ * ------------------------------------------------------------------------- */
+/* Attach the full-precision Cb and Cr (16-bit samples, values 0..1023, rows `stride`
+ * SAMPLES apart in both planes) to a resident picture. width x height is the LUMA size
+ * the picture was uploaded with; each plane holds (width + 1) >> 1 by (height + 1) >> 1
+ * samples. They are kept in a buffer of their own, replicated to W/2 x H/2 of the
+ * 8-aligned picture and by SVTME_PAD_CHROMA (40) on every side: the padding, and the
+ * deviation from the reference's 36, of svtme_picture_upload_chroma. Inside those 36
+ * the planes are what svt_aom_pack_highbd_pic makes of the reference's padded 8-bit
+ * and 2-bit chroma planes: pad_2b_compressed_input_picture and
+ * svt_aom_generate_padding_compressed_10bit repeat the edge sample's two bits where
+ * pad_input_picture and svt_aom_generate_padding repeat its eight. Synchronous,
+ * ordered after queued readers of the picture; released with the picture; dropped by
+ * whatever drops the 16-bit luma plane (a later luma upload, svtme_picture_invalidate,
+ * a svtme_tf_window or svtme_tf_window_yuv result under the number) and by a
+ * svtme_tf_window_10bit result under the number. svtme_picture_attach_10bit and this
+ * call may come in either order after the luma upload. Only the two calls below read
+ * the planes. Returns SVTME_ERR_BAD_PARAMETER before any GPU work for a NULL ctx / cb /
+ * cr, a zero size, a stride under the chroma width, a picture that is not resident or
+ * of another aligned size. */
+svtme_status svtme_picture_attach_chroma_10bit(svtme_ctx *ctx, uint64_t picture_number, const uint16_t *cb,
+                                               const uint16_t *cr, uint32_t stride, uint32_t width, uint32_t height);
+/* Copy a resident 16-bit chroma plane (1 = Cb, 2 = Cr) back in the shape of
+ * svtme_picture_download_chroma, in 16-bit samples: width x height are W/2 x H/2, pad
+ * SVTME_PAD_CHROMA, *stride = width + 2 pad in samples; dst NULL asks for the sizes
+ * alone. Fails for a picture without 16-bit chroma. */
+svtme_status svtme_picture_download_chroma_10bit(svtme_ctx *ctx, uint64_t picture_number, int plane, uint16_t *dst,
+                                                 uint32_t *stride, uint32_t *width, uint32_t *height, uint32_t *pad);
+
+/* The 16-bit form of svtme_tf_filter_yuv_out: strides in SAMPLES. */
+typedef struct svtme_tf_filter_yuv16_out {
+    uint16_t *y;        /* [height] rows of y_stride samples */
+    uint16_t *cb;       /* NULL, or [(height + 1) >> 1] rows of cb_stride samples, (width + 1) >> 1 written */
+    uint16_t *cr;       /* likewise */
+    uint32_t y_stride;  /* >= width */
+    uint32_t cb_stride; /* >= (width + 1) >> 1 where cb is set */
+    uint32_t cr_stride;
+    uint32_t pad;
+    uint32_t *err32;    /* NULL, or [n][SBs][4] as svtme_tf_filter_10bit's err32_out */
+} svtme_tf_filter_yuv16_out; /* 48 bytes */
+
+/* Host copies of a 10-bit window's filtered chroma; every pointer may be NULL. Strides in SAMPLES. */
+typedef struct svtme_tf_window_yuv16_out {
+    uint16_t *cb; /* [(src_height + 1) >> 1] rows of cb_stride samples */
+    uint16_t *cr;
+    uint32_t cb_stride;
+    uint32_t cr_stride;
+} svtme_tf_window_yuv16_out; /* 24 bytes */
+#ifdef __cplusplus
+static_assert(sizeof(svtme_tf_filter_yuv16_out) == 48 && sizeof(svtme_tf_window_yuv16_out) == 24,
+              "svtme_tf_*_yuv16 layout");
+#else
+_Static_assert(sizeof(svtme_tf_filter_yuv16_out) == 48 && sizeof(svtme_tf_window_yuv16_out) == 24,
+               "svtme_tf_*_yuv16 layout");
+#endif
+
+/* svtme_tf_filter_10bit with the chroma stage: the same arguments, the controls of
+ * svtme_tf_filter_yuv (the luma controls and the two chroma decay factors) and the
+ * outputs in a struct. out->y and out->err32 are byte for byte what
+ * svtme_tf_filter_10bit writes; out->cb and out->cr (either may be NULL) receive the
+ * filtered chroma at the true chroma size. Every picture of the window carries the
+ * 16-bit luma plane and the 16-bit chroma planes. No resident picture is modified.
+ * Synchronous. Refusals: those of svtme_tf_filter_10bit, and before any GPU work a
+ * chroma stride under the chroma width and a picture of the window without 16-bit
+ * chroma. */
+svtme_status svtme_tf_filter_yuv_10bit(svtme_ctx *ctx, uint64_t centre_picture_number,
+                                       const uint64_t *ref_picture_numbers, uint32_t n, uint32_t width,
+                                       uint32_t height, const svtme_tf_filter_yuv_controls *controls,
+                                       const svtme_tf_subpel_sb *subpel, const svtme_tf_filter_yuv16_out *out);
+
+/* svtme_tf_window_10bit with the chroma stage chained on lane 0's stream after the
+ * luma prediction. The result picture is what svtme_picture_upload_10bit +
+ * svtme_picture_attach_10bit + svtme_picture_attach_chroma_10bit of the filtered
+ * planes would leave: the chroma re-padded beyond the true chroma size and its margins
+ * too. In place (out_picture_number the centre's) all planes of the centre are
+ * replaced. 8-bit chroma under the result's number is dropped. `out`, plane16 and
+ * plane16_stride are svtme_tf_window_10bit's; out_uv may be NULL. The ordering
+ * guarantees, the asynchronous return when no host copy is asked for and the refusals
+ * are svtme_tf_window_10bit's; refused too, before any GPU work, are a chroma stride
+ * under the chroma width and a picture of the window without the 16-bit luma plane or
+ * without the 16-bit chroma planes. */
+svtme_status svtme_tf_window_yuv_10bit(svtme_ctx *ctx, const svtme_job *jobs, uint32_t n, uint32_t src_width,
+                                       uint32_t src_height, const svtme_tf_subpel_controls *subpel_controls,
+                                       const svtme_tf_filter_yuv_controls *filter_controls, uint64_t out_picture_number,
+                                       const svtme_tf_window_out *out, uint16_t *plane16, uint32_t plane16_stride,
+                                       const svtme_tf_window_yuv16_out *out_uv);
 
 /* Number of 64x64 SBs of a width x height picture, and R for a job. */
 uint32_t svtme_sb_total(uint32_t width, uint32_t height);

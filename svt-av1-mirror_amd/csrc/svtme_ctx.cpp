@@ -151,7 +151,7 @@ extern "C" svtme_status svtme_ctx_create(int device, svtme_ctx **out) {
     if ((e = svtme_prime_pyramid()) != hipSuccess || (e = svtme_prime_pack()) != hipSuccess ||
         (e = svtme_prime_stages()) != hipSuccess || (e = svtme_prime_dg()) != hipSuccess ||
         (e = svtme_prime_tfsp()) != hipSuccess || (e = svtme_prime_tff()) != hipSuccess ||
-        (e = svtme_prime_tffh()) != hipSuccess) {
+        (e = svtme_prime_tffh()) != hipSuccess || (e = svtme_prime_tffhc()) != hipSuccess) {
         (void)hipStreamDestroy(c->stream);
         delete c;
         return fail(SVTME_ERR_UNDEFINED, "svtme_ctx_create: loading the kernels: %s", hipGetErrorString(e));
@@ -193,6 +193,8 @@ static void free_pic(PicBuf &pb) {
         (void)hipFree(pb.cmem);
     if (pb.hmem)
         (void)hipFree(pb.hmem);
+    if (pb.hcmem)
+        (void)hipFree(pb.hcmem);
     if (pb.ready)
         (void)hipEventDestroy(pb.ready);
 }

@@ -2,7 +2,7 @@
 // of this is part of include/svtme.h.
 //
 //   svtme_ctx.cpp       error state, context create / destroy, lanes and streams, timing, host memory
-//   svtme_pictures.cpp  the picture pool, pyramid builds, every upload, release, download, chroma, 10-bit luma
+//   svtme_pictures.cpp  the picture pool, pyramid builds, every upload, release, download, chroma, 10-bit luma and chroma
 //   svtme_submit.cpp    job validation, the job-table ring, batch and packed submission, tickets, fetch
 //   svtme_windows.cpp   the picture-window calls: svtme_dg_detect and the temporal-filter stages
 //   svtme_controls.cpp  pure host code (no HIP): control derivation, the detector's reduction
@@ -36,6 +36,11 @@ struct PicBuf {
     uint8_t *hmem = nullptr;
     size_t hbytes = 0;
     DevPlane hbd{};
+    // attached full-precision chroma of a 10-bit picture (svtme_picture_attach_chroma_10bit,
+    // svtme_tf_window_yuv_10bit): a third buffer of its own, 16-bit samples (svtme_hbd_chroma_geometry)
+    uint8_t *hcmem = nullptr;
+    size_t hcbytes = 0;
+    DevPlane hchroma[2]{}; // Cb, Cr
     hipEvent_t ready = nullptr;          // end of an asynchronous upload on the upload stream
     uint32_t pending = 0;                 // lanes whose stream has not waited on `ready` yet
     hipEvent_t used[SVTME_LANES] = {};    // end of the last submission of each lane that reads the
@@ -190,9 +195,13 @@ svtme_status after_readers(svtme_ctx *c, PicBuf &pb, hipStream_t s); // `s` wait
 // `pb`, written on `s` (its `ready` exists): the lanes of `lanes` wait for that before they read it
 svtme_status upload_publish(PicBuf &pb, hipStream_t s, uint32_t lanes);
 svtme_status alloc_pic(svtme_ctx *c, uint64_t pn, uint32_t W, uint32_t H, PicBuf **out, bool keep_chroma = false,
-                       bool keep_hbd = false);
+                       bool keep_hbd = false, bool keep_hbd_chroma = false);
 svtme_status alloc_chroma(svtme_ctx *c, PicBuf &pb);
 svtme_status alloc_hbd(svtme_ctx *c, PicBuf &pb);
+svtme_status alloc_hbd_chroma(svtme_ctx *c, PicBuf &pb);
+// one padded 16-bit chroma plane from cw x ch true samples on the device (dsrc may be the plane's own interior)
+svtme_status build_hbd_chroma(const PicBuf *pb, int plane, const uint16_t *dsrc, uint32_t src_stride, uint32_t cw,
+                              uint32_t ch, hipStream_t st);
 // the padded 16-bit plane from w x h true samples on the device (dsrc may be the plane's own interior)
 svtme_status build_hbd(const PicBuf *pb, const uint16_t *dsrc, uint32_t src_stride, uint32_t w, uint32_t h,
                        hipStream_t st);

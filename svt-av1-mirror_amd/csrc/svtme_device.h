@@ -225,6 +225,18 @@ static inline void svtme_hbd_geometry(uint32_t W, uint32_t H, uint32_t *left, ui
     *rows   = H + 2 * *top;
 }
 
+// geometry of the attached 16-bit chroma planes (svtme_picture_attach_chroma_10bit; Cb and Cr alike) of
+// an aligned W x H picture, 4:2:0: the 8-bit chroma planes' in samples (48 left, at least 48 right, 40
+// rows above and below, the logical padding SVTME_PAD_CHROMA), two bytes a sample; `stride` is in bytes
+// (a multiple of 64; an interior row starts 96 bytes into its row, 16-byte aligned). A DevPlane
+// describes a plane as svtme_hbd_geometry's: stride in bytes, width, height and pad in samples.
+static inline void svtme_hbd_chroma_geometry(uint32_t W, uint32_t H, uint32_t *w, uint32_t *h, uint32_t *left,
+                                             uint32_t *top, uint32_t *stride, uint32_t *rows) {
+    *w = W / 2, *h = H / 2, *left = SVTME_DEV_C_LEFT, *top = SVTME_DEV_C_TOP;
+    *stride = svtme_round_up((W / 2 + SVTME_DEV_C_LEFT + 48) * 2, 64);
+    *rows   = *h + 2 * *top;
+}
+
 // Arguments of the chroma stage of temporal filtering (svtme_tff.hip: k_tff_pred_uv, k_tff_norm_uv,
 // k_tff_norm_uv_pic), filled by the host. Plane 0 is Cb, 1 is Cr; every picture of a window has the
 // same chroma geometry, so the references are base pointers with one stride.
@@ -245,6 +257,25 @@ struct TffcArgs {
     int32_t W, H;                                  // the 8-aligned luma size
 };
 
+// Arguments of the 10-bit chroma stage (svtme_tffhc.hip: k_tffh_pred_uv, k_tffh_norm_uv,
+// k_tffh_norm_uv_pic): TffcArgs on the 16-bit planes. Strides are in bytes, tiles and planes in samples.
+struct TffhcArgs {
+    DevPlane cen_y;                                // the centre picture's 16-bit luma plane
+    DevPlane cen[2];                               // its 16-bit chroma planes
+    const uint8_t *ref[2][SVTME_MAX_BATCH_JOBS];   // interior sample (0, 0) of the references' 16-bit chroma planes
+    int32_t ref_stride;                            // bytes
+    const svtme_tf_subpel_sb *sub;                 // [n][sbs]
+    const uint16_t *tile_y;                        // [n][sbs][64 * 64] luma predictions (k_tffh_pred)
+    const uint32_t *e32;                           // [n][sbs][4] 32x32 errors (k_tffh_pred)
+    uint16_t *tile;                                // [n][sbs][2][32 * 32] chroma predictions
+    uint32_t *wgt;                                 // [n][sbs][2][16] chroma weights
+    uint16_t *plane;                               // k_tffh_norm_uv: [2] planes of whole SBs, pic_w_b64 * 32 samples a row
+    DevPlane dst[2];                               // k_tffh_norm_uv_pic: the result picture's 16-bit chroma (may be cen)
+    uint32_t decay_cb, decay_cr, dist_th;
+    uint32_t n, sbs, pic_w_b64;
+    int32_t W, H;                                  // the 8-aligned luma size
+};
+
 // Bytes per unit (one reference's SB) of the temporal filter's scratch sections, as svtme_tff.hip
 // indexes them; the host lays the sections out by these (TfScratch, svtme_windows.cpp).
 #define SVTME_TFF_TILE_BYTES 4096   // luma prediction: k_tff_pred / k_tff_norm, `A.tile + unit * 4096`
@@ -256,3 +287,6 @@ struct TffcArgs {
 // (the dense luma plane of k_tff_norm holds SVTME_TFF_TILE_BYTES per SB: whole 64 x 64 SBs)
 #define SVTME_TFFH_TILE_BYTES 8192  // 16-bit luma prediction: k_tffh_pred / k_tffh_norm, `A.tile + unit * 4096` samples
 // (svtme_tffh.hip shares the weight and error sections; its dense plane holds SVTME_TFFH_TILE_BYTES per SB)
+#define SVTME_TFFHC_TILE_BYTES 4096 // 16-bit Cb and Cr predictions: k_tffh_pred_uv / k_tffh_norm_uv, `A.tile + unit * 2048` samples
+#define SVTME_TFFHC_PLANE_SB_BYTES 2048 // one SB of one dense 16-bit chroma plane: k_tffh_norm_uv, `pl * A.sbs * 1024` samples
+// (svtme_tffhc.hip's weights hold SVTME_TFFC_WGT_BYTES per unit, as the 8-bit chroma stage's)

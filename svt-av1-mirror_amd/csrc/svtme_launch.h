@@ -162,4 +162,12 @@ hipError_t svtme_launch_tffh_pic(const DevPlane *cen, const DevPlane *ref, uint3
                                  const svtme_tf_filter_controls *ctl, const svtme_tf_subpel_sb *d_sub, uint16_t *d_tile,
                                  uint32_t *d_wgt, uint32_t *d_e32, const DevPlane *dst, const DevPlane *dst8,
                                  hipStream_t s);
+// svtme_tffhc.hip: the 10-bit chroma stage. svtme_launch_tffhc follows svtme_launch_tffh on `s`;
+// svtme_launch_tffh_pic_yuv is svtme_launch_tffh_pic with the chroma stage between and after its two steps
+hipError_t svtme_prime_tffhc(void);
+hipError_t svtme_launch_tffhc(const TffhcArgs *A, hipStream_t s);
+hipError_t svtme_launch_tffh_pic_yuv(const DevPlane *cen, const DevPlane *ref, uint32_t n, uint32_t width,
+                                     uint32_t height, const svtme_tf_filter_controls *ctl,
+                                     const svtme_tf_subpel_sb *d_sub, uint16_t *d_tile, uint32_t *d_wgt, uint32_t *d_e32,
+                                     const DevPlane *dst, const DevPlane *dst8, const TffhcArgs *U, hipStream_t s);
 }

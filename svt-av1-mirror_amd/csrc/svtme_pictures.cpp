@@ -74,6 +74,8 @@ static uint8_t *sweep_graves(svtme_ctx *c, size_t want) {
             give_free(c, g.cbytes, g.cmem);
         if (g.hmem) // the 16-bit plane likewise
             give_free(c, g.hbytes, g.hmem);
+        if (g.hcmem) // and the 16-bit chroma
+            give_free(c, g.hcbytes, g.hcmem);
         c->graves[i] = c->graves.back();
         c->graves.pop_back();
     }
@@ -193,16 +195,58 @@ svtme_status svtme_host::alloc_hbd(svtme_ctx *c, PicBuf &pb) {
     return SVTME_OK;
 }
 
-// allocate the three planes of a W x H picture in one buffer; chroma and the 16-bit plane attached to
-// an earlier picture of the number are dropped unless the caller writes them too (svtme_tf_window_yuv,
-// svtme_tf_window_10bit)
+// bytes of the two padded 16-bit chroma planes of a W x H picture in one buffer, and the second's offset
+static size_t hbd_chroma_bytes(uint32_t W, uint32_t H, size_t *second = nullptr) {
+    uint32_t w, h, left, top, stride, rows;
+    svtme_hbd_chroma_geometry(W, H, &w, &h, &left, &top, &stride, &rows);
+    const size_t one = align256((size_t)stride * rows);
+    if (second)
+        *second = one;
+    return 2 * one + 256; // slack: the staging's aligned dword pairs end inside the row
+}
+
+// The picture's luma is about to be replaced: its 16-bit chroma no longer belongs to it (drop_chroma's way)
+static void drop_hbd_chroma(svtme_ctx *c, PicBuf &pb) {
+    if (!pb.hcmem)
+        return;
+    PicBuf g;
+    g.mem = pb.hcmem, g.bytes = pb.hcbytes;
+    for (int l = 0; l < SVTME_LANES; l++) g.used[l] = pb.used[l];
+    c->graves.push_back(g);
+    pb.hcmem = nullptr, pb.hcbytes = 0;
+    pb.hchroma[0] = pb.hchroma[1] = DevPlane{};
+}
+
+// 16-bit chroma planes for a resident picture that has none (contents undefined until written)
+svtme_status svtme_host::alloc_hbd_chroma(svtme_ctx *c, PicBuf &pb) {
+    if (pb.hcmem)
+        return SVTME_OK;
+    size_t second;
+    const size_t total = hbd_chroma_bytes(pb.W, pb.H, &second);
+    svtme_status st    = pic_mem(c, total, &pb.hcmem);
+    if (st)
+        return st;
+    pb.hcbytes = total;
+    uint32_t w, h, left, top, stride, rows;
+    svtme_hbd_chroma_geometry(pb.W, pb.H, &w, &h, &left, &top, &stride, &rows);
+    for (int p = 0; p < 2; p++)
+        pb.hchroma[p] = DevPlane{pb.hcmem + p * second + (size_t)top * stride + (size_t)left * 2, (int32_t)stride,
+                                 (int32_t)w, (int32_t)h, SVTME_PAD_CHROMA};
+    return SVTME_OK;
+}
+
+// allocate the three planes of a W x H picture in one buffer; chroma, the 16-bit plane and the 16-bit
+// chroma attached to an earlier picture of the number are dropped unless the caller writes them too
+// (svtme_tf_window_yuv, svtme_tf_window_10bit, svtme_tf_window_yuv_10bit)
 svtme_status svtme_host::alloc_pic(svtme_ctx *c, uint64_t pn, uint32_t W, uint32_t H, PicBuf **out,
-                                   bool keep_chroma, bool keep_hbd) {
+                                   bool keep_chroma, bool keep_hbd, bool keep_hbd_chroma) {
     auto it = c->pics.find(pn);
     if (it != c->pics.end() && it->second.W == W && it->second.H == H && !keep_chroma)
         drop_chroma(c, it->second);
     if (it != c->pics.end() && it->second.W == W && it->second.H == H && !keep_hbd)
         drop_hbd(c, it->second);
+    if (it != c->pics.end() && it->second.W == W && it->second.H == H && !keep_hbd_chroma)
+        drop_hbd_chroma(c, it->second);
     if (it != c->pics.end() && (it->second.W != W || it->second.H != H)) {
         // a new size: the old buffer goes to the graves (freed for reuse once its readers ran)
         c->graves.push_back(it->second);
@@ -697,4 +741,65 @@ extern "C" svtme_status svtme_picture_download_10bit(svtme_ctx *c, uint64_t pn, 
         return fail(SVTME_ERR_BAD_PARAMETER, "svtme_picture_download_10bit: picture %llu %s", (unsigned long long)pn,
                     !pb ? "is not resident" : "has no 10-bit plane");
     return download_plane(c, pb->hbd, dst, stride, width, height, pad, 2);
+}
+
+// ---- the full-precision chroma of a 10-bit picture ----
+// k_build_full16 takes its geometry as parameters: the chroma margins serve it as the luma's do
+svtme_status svtme_host::build_hbd_chroma(const PicBuf *pb, int plane, const uint16_t *dsrc, uint32_t src_stride,
+                                          uint32_t cw, uint32_t ch, hipStream_t st) {
+    uint32_t w, h, left, top, stride, rows;
+    svtme_hbd_chroma_geometry(pb->W, pb->H, &w, &h, &left, &top, &stride, &rows);
+    HIP_TRY(svtme_launch_build_full16(dsrc, src_stride, (int)cw, (int)ch, pb->hchroma[plane], (int)left, (int)top,
+                                      (int)rows, st));
+    return SVTME_OK;
+}
+
+extern "C" svtme_status svtme_picture_attach_chroma_10bit(svtme_ctx *c, uint64_t pn, const uint16_t *cb,
+                                                          const uint16_t *cr, uint32_t stride, uint32_t w, uint32_t h) {
+    const char *fn = "svtme_picture_attach_chroma_10bit";
+    if (!c || !cb || !cr || w == 0 || h == 0)
+        return fail(SVTME_ERR_BAD_PARAMETER, "%s: null ctx, cb or cr, or a %ux%u picture", fn, w, h);
+    const uint32_t cw = (w + 1) >> 1, ch = (h + 1) >> 1;
+    if (stride < cw)
+        return fail(SVTME_ERR_BAD_PARAMETER, "%s: stride %u under the chroma width %u", fn, stride, cw);
+    std::lock_guard<std::mutex> lk(c->mu);
+    PicBuf *pbp = find_pic(c, pn);
+    if (!pbp)
+        return fail(SVTME_ERR_BAD_PARAMETER, "%s: picture %llu is not resident", fn, (unsigned long long)pn);
+    PicBuf &pb = *pbp;
+    if (pb.W != svtme_align8_u(w) || pb.H != svtme_align8_u(h))
+        return fail(SVTME_ERR_BAD_PARAMETER, "%s: picture %llu is %ux%u, the chroma's %ux%u", fn, (unsigned long long)pn,
+                    pb.W, pb.H, w, h);
+    HIP_TRY(hipSetDevice(c->device));
+    svtme_status st;
+    const size_t one = (size_t)cw * ch; // samples
+    if ((st = alloc_hbd_chroma(c, pb)) || (st = ensure_buf(&c->staging, &c->staging_cap, 4 * one)))
+        return st;
+    uint16_t *stg = (uint16_t *)c->staging; // (reused in stream order, as upload_sync does)
+    HIP_TRY(hipMemcpy2DAsync(stg, (size_t)cw * 2, cb, (size_t)stride * 2, (size_t)cw * 2, ch, hipMemcpyHostToDevice,
+                             c->stream));
+    HIP_TRY(hipMemcpy2DAsync(stg + one, (size_t)cw * 2, cr, (size_t)stride * 2, (size_t)cw * 2, ch,
+                             hipMemcpyHostToDevice, c->stream));
+    // queued jobs of the other lanes may still read the old planes (lane 0's run before by stream order)
+    if ((st = after_readers(c, pb, c->stream)) || (st = build_hbd_chroma(&pb, 0, stg, cw, cw, ch, c->stream)) ||
+        (st = build_hbd_chroma(&pb, 1, stg + one, cw, cw, ch, c->stream)))
+        return st;
+    // later jobs of the other lanes wait for the planes: the stream is drained before the call returns
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return SVTME_OK;
+}
+
+// Copy one 16-bit chroma plane back in the shape of svtme_picture_download_10bit; the stride is in samples
+extern "C" svtme_status svtme_picture_download_chroma_10bit(svtme_ctx *c, uint64_t pn, int plane, uint16_t *dst,
+                                                            uint32_t *stride, uint32_t *width, uint32_t *height,
+                                                            uint32_t *pad) {
+    const char *fn = "svtme_picture_download_chroma_10bit";
+    if (!c || plane < 1 || plane > 2)
+        return fail(SVTME_ERR_BAD_PARAMETER, "%s: null ctx or plane %d (1 = Cb, 2 = Cr)", fn, plane);
+    std::lock_guard<std::mutex> lk(c->mu);
+    const PicBuf *pb = find_pic(c, pn);
+    if (!pb || !pb->hcmem)
+        return fail(SVTME_ERR_BAD_PARAMETER, "%s: picture %llu %s", fn, (unsigned long long)pn,
+                    !pb ? "is not resident" : "has no 10-bit chroma");
+    return download_plane(c, pb->hchroma[plane - 1], dst, stride, width, height, pad, 2);
 }

@@ -1,5 +1,6 @@
 // svtme_windows.cpp — the calls over a window of resident pictures, all on lane 0: the dynamic-GOP
-// detector (svtme_dg.hip) and temporal filtering's stages (svtme_tfsp.hip, svtme_tff.hip, svtme_tffh.hip), alone
+// detector (svtme_dg.hip) and temporal filtering's stages (svtme_tfsp.hip, svtme_tff.hip, svtme_tffh.hip,
+// svtme_tffhc.hip), alone
 // and as one window resident to resident. Each holds the context lock from its first launch to
 // its last copy, as svtme_submit_picture does: the device outputs are the context's, and a
 // release / invalidate of a picture from another thread waits for the lock.
@@ -67,9 +68,10 @@ extern "C" svtme_status svtme_dg_detect(svtme_ctx *c, const svtme_dg_pair *pairs
 // ---- what the temporal-filter calls share ----
 // The resident pictures pn[0..count) of a window, each W x H (8-aligned) and, where the call
 // filters chroma, with chroma attached, where it filters 10-bit luma, with the 16-bit plane
-// attached. The first picture that fails decides the message.
+// attached, where it filters 10-bit chroma, with the 16-bit chroma planes attached. The first picture
+// that fails decides the message.
 static svtme_status resident_pics(svtme_ctx *c, const char *fn, const uint64_t *pn, uint32_t count, uint32_t W,
-                                  uint32_t H, bool chroma, PicBuf **pb, bool hbd = false) {
+                                  uint32_t H, bool chroma, PicBuf **pb, bool hbd = false, bool hbd_chroma = false) {
     for (uint32_t k = 0; k < count; k++) {
         if (!(pb[k] = find_pic(c, pn[k])))
             return fail(SVTME_ERR_BAD_PARAMETER, "%s: picture %llu is not resident", fn, (unsigned long long)pn[k]);
@@ -80,6 +82,8 @@ static svtme_status resident_pics(svtme_ctx *c, const char *fn, const uint64_t *
             return fail(SVTME_ERR_BAD_PARAMETER, "%s: picture %llu has no chroma", fn, (unsigned long long)pn[k]);
         if (hbd && !pb[k]->hmem)
             return fail(SVTME_ERR_BAD_PARAMETER, "%s: picture %llu has no 10-bit plane", fn, (unsigned long long)pn[k]);
+        if (hbd_chroma && !pb[k]->hcmem)
+            return fail(SVTME_ERR_BAD_PARAMETER, "%s: picture %llu has no 10-bit chroma", fn, (unsigned long long)pn[k]);
     }
     return SVTME_OK;
 }
@@ -119,7 +123,8 @@ static svtme_status tff_controls_check(const char *fn, const char *what, const s
 //   results of the sub-pel stage | luma tiles | weights | errors | (dense) the luma plane, whole SBs |
 //   (chroma) Cb and Cr tiles | weights | (chroma, dense) the two planes, whole SBs
 // (704 bytes a result, multiples of 16 per unit or SB elsewhere: the sections stay 16-byte aligned).
-// The 10-bit calls (hbd) hold 16-bit luma tiles and a 16-bit dense plane in the same places.
+// The 10-bit calls (hbd) hold 16-bit luma tiles and a 16-bit dense plane in the same places, and with
+// chroma 16-bit chroma tiles and dense planes.
 // The stage calls copy dense planes out; the window call writes the result picture and has none.
 struct TfScratch {
     svtme_tf_subpel_sb *sub;
@@ -134,7 +139,7 @@ static svtme_status tf_scratch(svtme_ctx *c, uint32_t n, uint32_t sbs, bool dens
     const size_t units = (size_t)n * sbs;
     S->sub_bytes    = sizeof(svtme_tf_subpel_sb) * units;
     S->e32_bytes    = SVTME_TFF_E32_BYTES * units;
-    S->cplane_bytes = (size_t)SVTME_TFFC_PLANE_SB_BYTES * sbs;
+    S->cplane_bytes = (size_t)(hbd ? SVTME_TFFHC_PLANE_SB_BYTES : SVTME_TFFC_PLANE_SB_BYTES) * sbs;
     size_t end = 0;
     auto take  = [&end](bool present, size_t bytes) { // the section's offset; absent sections are empty
         const size_t at = end;
@@ -142,10 +147,11 @@ static svtme_status tf_scratch(svtme_ctx *c, uint32_t n, uint32_t sbs, bool dens
         return at;
     };
     const size_t tile_bytes = hbd ? SVTME_TFFH_TILE_BYTES : SVTME_TFF_TILE_BYTES;
+    const size_t ctile_bytes = hbd ? SVTME_TFFHC_TILE_BYTES : SVTME_TFFC_TILE_BYTES;
     const size_t o_sub = take(true, S->sub_bytes), o_tile = take(true, tile_bytes * units),
                  o_wgt = take(true, SVTME_TFF_WGT_BYTES * units), o_e32 = take(true, S->e32_bytes),
                  o_plane = take(dense, tile_bytes * sbs),
-                 o_ctile = take(chroma, SVTME_TFFC_TILE_BYTES * units),
+                 o_ctile = take(chroma, ctile_bytes * units),
                  o_cwgt = take(chroma, SVTME_TFFC_WGT_BYTES * units),
                  o_cplane = take(chroma && dense, 2 * S->cplane_bytes);
     svtme_status st = ensure_buf(&c->d_tff, &c->tff_cap, end);
@@ -158,7 +164,8 @@ static svtme_status tf_scratch(svtme_ctx *c, uint32_t n, uint32_t sbs, bool dens
     return SVTME_OK;
 }
 
-// the chroma side of svtme_tf_filter_yuv / svtme_tf_window_yuv: the decay factors and the host copies
+// the chroma side of the yuv calls: the decay factors and the host copies. In the 10-bit yuv calls (a
+// TfHbd beside it) `out` holds uint16_t planes and the strides are in samples.
 struct TfChroma {
     uint32_t decay[2];
     uint8_t *out[2]; // Cb, Cr; either may be NULL
@@ -195,6 +202,31 @@ static void tffc_fill(TffcArgs &A, PicBuf *const *pb, uint32_t n, uint32_t W, ui
     A.tile       = S.ctile;
     A.wgt        = S.cwgt;
     A.plane      = S.cplane;
+    A.decay_cb   = uv->decay[0];
+    A.decay_cr   = uv->decay[1];
+    A.dist_th    = ctl->tf_mv_dist_th;
+    A.n          = n;
+    A.pic_w_b64  = (W + 63) / 64;
+    A.sbs        = svtme_sb_total(W, H);
+    A.W          = (int32_t)W;
+    A.H          = (int32_t)H;
+}
+
+// the 10-bit chroma stage's arguments likewise (the luma tiles and planes are the 16-bit ones)
+static void tffhc_fill(TffhcArgs &A, PicBuf *const *pb, uint32_t n, uint32_t W, uint32_t H,
+                       const svtme_tf_filter_controls *ctl, const TfChroma *uv, const TfScratch &S) {
+    A.cen_y = pb[0]->hbd;
+    for (int p = 0; p < 2; p++) {
+        A.cen[p] = pb[0]->hchroma[p];
+        for (uint32_t k = 0; k < SVTME_MAX_BATCH_JOBS; k++) A.ref[p][k] = pb[k < n ? k + 1 : 1]->hchroma[p].base;
+    }
+    A.ref_stride = pb[1]->hchroma[0].stride;
+    A.sub        = S.sub;
+    A.tile_y     = (const uint16_t *)S.tile;
+    A.e32        = S.e32;
+    A.tile       = (uint16_t *)S.ctile;
+    A.wgt        = S.cwgt;
+    A.plane      = (uint16_t *)S.cplane;
     A.decay_cb   = uv->decay[0];
     A.decay_cr   = uv->decay[1];
     A.dist_th    = ctl->tf_mv_dist_th;
@@ -249,8 +281,8 @@ extern "C" svtme_status svtme_tf_subpel(svtme_ctx *c, uint64_t centre_picture_nu
 }
 
 // ---- Temporal filtering's prediction and weighting (svtme_tff.hip) ----
-// svtme_tf_filter (uv and hb NULL), svtme_tf_filter_yuv (uv) and svtme_tf_filter_10bit (hb: `out` and
-// `out_stride` are hb's, the stride in samples)
+// svtme_tf_filter (uv and hb NULL), svtme_tf_filter_yuv (uv), svtme_tf_filter_10bit (hb: `out` and
+// `out_stride` are hb's, the stride in samples) and svtme_tf_filter_yuv_10bit (both)
 static svtme_status tf_filter_impl(const char *fn, const TfChroma *uv, const TfHbd *hb, svtme_ctx *c,
                                    uint64_t centre_picture_number,
                                    const uint64_t *ref_picture_numbers, uint32_t n, uint32_t width, uint32_t height,
@@ -278,7 +310,7 @@ static svtme_status tf_filter_impl(const char *fn, const TfChroma *uv, const TfH
     memcpy(pn + 1, ref_picture_numbers, n * sizeof(uint64_t));
     std::lock_guard<std::mutex> lk(c->mu);
     PicBuf *pb[SVTME_MAX_BATCH_JOBS + 1];
-    if ((st = resident_pics(c, fn, pn, n + 1, W, H, uv != nullptr, pb, hb != nullptr)))
+    if ((st = resident_pics(c, fn, pn, n + 1, W, H, uv && !hb, pb, hb != nullptr, uv && hb)))
         return st;
     HIP_TRY(hipSetDevice(c->device));
     TfScratch S;
@@ -294,7 +326,11 @@ static svtme_status tf_filter_impl(const char *fn, const TfChroma *uv, const TfH
                                   (uint16_t *)S.plane, L.s));
     } else
         HIP_TRY(svtme_launch_tff(&pb[0]->pyr.lv[0], ref, n, W, H, ctl, S.sub, S.tile, S.wgt, S.e32, S.plane, L.s));
-    if (uv) {
+    if (uv && hb) {
+        TffhcArgs U{};
+        tffhc_fill(U, pb, n, W, H, ctl, uv, S);
+        HIP_TRY(svtme_launch_tffhc(&U, L.s));
+    } else if (uv) {
         TffcArgs U{};
         tffc_fill(U, pb, n, W, H, ctl, uv, S);
         HIP_TRY(svtme_launch_tffc(&U, L.s));
@@ -310,8 +346,8 @@ static svtme_status tf_filter_impl(const char *fn, const TfChroma *uv, const TfH
         HIP_TRY(hipMemcpyAsync(err32_out, S.e32, S.e32_bytes, hipMemcpyDeviceToHost, L.s));
     for (int p = 0; uv && p < 2; p++)
         if (uv->out[p])
-            HIP_TRY(hipMemcpy2DAsync(uv->out[p], uv->stride[p], S.cplane + p * S.cplane_bytes, pstride / 2,
-                                     (width + 1) >> 1, (height + 1) >> 1, hipMemcpyDeviceToHost, L.s));
+            HIP_TRY(hipMemcpy2DAsync(uv->out[p], uv->stride[p] * bpp, S.cplane + p * S.cplane_bytes, pstride / 2 * bpp,
+                                     ((width + 1) >> 1) * bpp, (height + 1) >> 1, hipMemcpyDeviceToHost, L.s));
     HIP_TRY(hipStreamSynchronize(L.s));
     return SVTME_OK;
 }
@@ -353,8 +389,9 @@ extern "C" svtme_status svtme_tf_filter_10bit(svtme_ctx *c, uint64_t centre_pict
 // k_tff_pred and the normalisation into the result picture, chained by lane 0's
 // stream through the two stages' scratch.
 // ----------------------------------------------------------------------------
-// svtme_tf_window (uv and hb NULL), svtme_tf_window_yuv (uv) and svtme_tf_window_10bit (hb: the TF-ME
-// batch and k_tfsp on the MSB planes as ever, then svtme_tffh.hip on the 16-bit planes)
+// svtme_tf_window (uv and hb NULL), svtme_tf_window_yuv (uv), svtme_tf_window_10bit (hb: the TF-ME
+// batch and k_tfsp on the MSB planes as ever, then svtme_tffh.hip on the 16-bit planes) and
+// svtme_tf_window_yuv_10bit (both: svtme_tffhc.hip's chroma stage beside it)
 static svtme_status tf_window_impl(const char *fn, const TfChroma *uv, const TfHbd *hb, svtme_ctx *c,
                                    const svtme_job *jobs, uint32_t n,
                                    uint32_t src_width, uint32_t src_height, const svtme_tf_subpel_controls *sp_ctl,
@@ -409,7 +446,8 @@ static svtme_status tf_window_impl(const char *fn, const TfChroma *uv, const TfH
     // the batch and the result picture's allocation: std::map keeps its other nodes where they
     // are, and the result picture, where it is the centre, has the centre's size and stays too.
     PicBuf *pb[SVTME_MAX_BATCH_JOBS + 1];
-    if ((st = resident_pics(c, fn, pn, n + 1, W, H, uv != nullptr, pb, hb != nullptr)))
+    const bool uv8 = uv && !hb, uv16 = uv && hb;
+    if ((st = resident_pics(c, fn, pn, n + 1, W, H, uv8, pb, hb != nullptr, uv16)))
         return st;
     HIP_TRY(hipSetDevice(c->device));
     // the sub-pel scratch holds the records (its results go to the filter's scratch)
@@ -425,8 +463,8 @@ static svtme_status tf_window_impl(const char *fn, const TfChroma *uv, const TfH
         return st;
     // the result picture (a new number: a buffer of the pool)
     PicBuf *po;
-    if ((st = alloc_pic(c, out_pn, W, H, &po, uv != nullptr, hb != nullptr)) || (uv && (st = alloc_chroma(c, *po))) ||
-        (hb && (st = alloc_hbd(c, *po))))
+    if ((st = alloc_pic(c, out_pn, W, H, &po, uv8, hb != nullptr, uv16)) || (uv8 && (st = alloc_chroma(c, *po))) ||
+        (hb && (st = alloc_hbd(c, *po))) || (uv16 && (st = alloc_hbd_chroma(c, *po))))
         return st;
     Lane &L = c->lanes[0];
     DevPlane ref[SVTME_MAX_BATCH_JOBS];
@@ -435,7 +473,22 @@ static svtme_status tf_window_impl(const char *fn, const TfChroma *uv, const TfH
     if ((st = join_upload(c, *po, 0)) || (st = after_readers(c, *po, L.s)))
         return st;
     HIP_TRY(svtme_launch_tfsp(&pb[0]->pyr.lv[0], ref, n, W, H, sp_ctl, d_rec, S.sub, L.s));
-    if (uv) {
+    if (uv16) {
+        DevPlane ref16[SVTME_MAX_BATCH_JOBS];
+        for (uint32_t k = 0; k < n; k++) ref16[k] = pb[k + 1]->hbd;
+        TffhcArgs U{};
+        tffhc_fill(U, pb, n, W, H, f_ctl, uv, S);
+        U.dst[0] = po->hchroma[0], U.dst[1] = po->hchroma[1];
+        HIP_TRY(svtme_launch_tffh_pic_yuv(&pb[0]->hbd, ref16, n, W, H, f_ctl, S.sub, (uint16_t *)S.tile, S.wgt, S.e32,
+                                          &po->hbd, &po->pyr.lv[0], &U, L.s));
+        // the 16-bit planes beyond their true sizes and their margins, from their own interiors
+        if ((st = build_hbd(po, (const uint16_t *)po->hbd.base, (uint32_t)po->hbd.stride / 2, src_width, src_height, L.s)))
+            return st;
+        for (int p = 0; p < 2; p++)
+            if ((st = build_hbd_chroma(po, p, (const uint16_t *)po->hchroma[p].base, (uint32_t)po->hchroma[p].stride / 2,
+                                       (src_width + 1) >> 1, (src_height + 1) >> 1, L.s)))
+                return st;
+    } else if (uv) {
         // both predictions before either normalisation: in place the chroma stage reads the centre's luma
         TffcArgs U{};
         tffc_fill(U, pb, n, W, H, f_ctl, uv, S);
@@ -457,7 +510,7 @@ static svtme_status tf_window_impl(const char *fn, const TfChroma *uv, const TfH
     if ((st = build_pyramid(c, po, po->pyr.lv[0].base, (uint32_t)po->pyr.lv[0].stride, src_width, src_height, 0, L.s)))
         return st;
     // the chroma planes likewise: beyond the true chroma size and the margins, from their own interior
-    for (int p = 0; uv && p < 2; p++)
+    for (int p = 0; uv8 && p < 2; p++)
         if ((st = build_chroma(po, p, po->chroma[p].base, (uint32_t)po->chroma[p].stride, (src_width + 1) >> 1,
                                (src_height + 1) >> 1, L.s)))
             return st;
@@ -487,10 +540,13 @@ static svtme_status tf_window_impl(const char *fn, const TfChroma *uv, const TfH
     if (want_16)
         HIP_TRY(hipMemcpy2DAsync(hb->out, (size_t)hb->stride * 2, po->hbd.base, (size_t)po->hbd.stride,
                                  (size_t)src_width * 2, src_height, hipMemcpyDeviceToHost, L.s));
-    for (int p = 0; want_uv && p < 2; p++)
+    for (int p = 0; want_uv && p < 2; p++) {
+        const DevPlane &cp = uv16 ? po->hchroma[p] : po->chroma[p];
+        const size_t bpp   = uv16 ? 2 : 1;
         if (uv->out[p])
-            HIP_TRY(hipMemcpy2DAsync(uv->out[p], uv->stride[p], po->chroma[p].base, (size_t)po->chroma[p].stride,
-                                     (src_width + 1) >> 1, (src_height + 1) >> 1, hipMemcpyDeviceToHost, L.s));
+            HIP_TRY(hipMemcpy2DAsync(uv->out[p], uv->stride[p] * bpp, cp.base, (size_t)cp.stride,
+                                     ((src_width + 1) >> 1) * bpp, (src_height + 1) >> 1, hipMemcpyDeviceToHost, L.s));
+    }
     HIP_TRY(hipStreamSynchronize(L.s));
     return SVTME_OK;
 }
@@ -522,4 +578,33 @@ extern "C" svtme_status svtme_tf_window_10bit(svtme_ctx *c, const svtme_job *job
     const TfHbd hb = {plane16, plane16_stride};
     return tf_window_impl("svtme_tf_window_10bit", nullptr, &hb, c, jobs, n, src_width, src_height, sp_ctl, f_ctl, out_pn,
                           out);
+}
+
+extern "C" svtme_status svtme_tf_filter_yuv_10bit(svtme_ctx *c, uint64_t centre_picture_number,
+                                                  const uint64_t *ref_picture_numbers, uint32_t n, uint32_t width,
+                                                  uint32_t height, const svtme_tf_filter_yuv_controls *ctl,
+                                                  const svtme_tf_subpel_sb *subpel, const svtme_tf_filter_yuv16_out *out) {
+    if (!ctl || !out)
+        return fail(SVTME_ERR_BAD_PARAMETER, "svtme_tf_filter_yuv_10bit: null controls or out");
+    const TfChroma uv = {{ctl->tf_decay_factor_cb_fp16, ctl->tf_decay_factor_cr_fp16},
+                         {(uint8_t *)out->cb, (uint8_t *)out->cr},
+                         {out->cb_stride, out->cr_stride}};
+    const TfHbd hb    = {out->y, out->y_stride};
+    return tf_filter_impl("svtme_tf_filter_yuv_10bit", &uv, &hb, c, centre_picture_number, ref_picture_numbers, n, width,
+                          height, &ctl->luma, subpel, (uint8_t *)out->y, out->y_stride, out->err32);
+}
+
+extern "C" svtme_status svtme_tf_window_yuv_10bit(svtme_ctx *c, const svtme_job *jobs, uint32_t n, uint32_t src_width,
+                                                  uint32_t src_height, const svtme_tf_subpel_controls *sp_ctl,
+                                                  const svtme_tf_filter_yuv_controls *f_ctl, uint64_t out_pn,
+                                                  const svtme_tf_window_out *out, uint16_t *plane16,
+                                                  uint32_t plane16_stride, const svtme_tf_window_yuv16_out *out_uv) {
+    if (!f_ctl)
+        return fail(SVTME_ERR_BAD_PARAMETER, "svtme_tf_window_yuv_10bit: null filter_controls");
+    const TfChroma uv = {{f_ctl->tf_decay_factor_cb_fp16, f_ctl->tf_decay_factor_cr_fp16},
+                         {out_uv ? (uint8_t *)out_uv->cb : nullptr, out_uv ? (uint8_t *)out_uv->cr : nullptr},
+                         {out_uv ? out_uv->cb_stride : 0, out_uv ? out_uv->cr_stride : 0}};
+    const TfHbd hb    = {plane16, plane16_stride};
+    return tf_window_impl("svtme_tf_window_yuv_10bit", &uv, &hb, c, jobs, n, src_width, src_height, sp_ctl, &f_ctl->luma,
+                          out_pn, out);
 }

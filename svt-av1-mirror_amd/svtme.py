@@ -313,6 +313,18 @@ class TfWindowYuvOut(C.Structure):
     _fields_ = [("cb", C.c_void_p), ("cr", C.c_void_p), ("cb_stride", C.c_uint32), ("cr_stride", C.c_uint32)]
 
 
+class TfFilterYuv16Out(C.Structure):
+    """svtme_tf_filter_yuv16_out: where svtme_tf_filter_yuv_10bit writes, strides in samples; cb, cr and
+    err32 may be NULL."""
+    _fields_ = [("y", C.c_void_p), ("cb", C.c_void_p), ("cr", C.c_void_p), ("y_stride", C.c_uint32),
+                ("cb_stride", C.c_uint32), ("cr_stride", C.c_uint32), ("pad", C.c_uint32), ("err32", C.c_void_p)]
+
+
+class TfWindowYuv16Out(C.Structure):
+    """svtme_tf_window_yuv16_out: host copies of a 10-bit window's filtered chroma, strides in samples."""
+    _fields_ = [("cb", C.c_void_p), ("cr", C.c_void_p), ("cb_stride", C.c_uint32), ("cr_stride", C.c_uint32)]
+
+
 TAIL_BYTES = 24  # svtme_record_tail: the last 24 bytes of svtme_ref_record
 
 
@@ -792,6 +804,22 @@ def _job_api_protos(lib):
                                                           C.POINTER(TfSubpelControls), C.POINTER(TfFilterControls),
                                                           C.c_uint64, C.POINTER(TfWindowOut), vp, C.c_uint32])
         _proto(lib, "svtme_tf_window_10bit", "restype", C.c_int32)
+        _proto(lib, "svtme_picture_attach_chroma_10bit", "argtypes", [vp, C.c_uint64, vp, vp, C.c_uint32, C.c_uint32,
+                                                                      C.c_uint32])
+        _proto(lib, "svtme_picture_attach_chroma_10bit", "restype", C.c_int32)
+        _proto(lib, "svtme_picture_download_chroma_10bit", "argtypes", [vp, C.c_uint64, C.c_int, vp] +
+               [C.POINTER(C.c_uint32)] * 4)
+        _proto(lib, "svtme_picture_download_chroma_10bit", "restype", C.c_int32)
+        _proto(lib, "svtme_tf_filter_yuv_10bit", "argtypes", [vp, C.c_uint64, C.POINTER(C.c_uint64), C.c_uint32,
+                                                              C.c_uint32, C.c_uint32, C.POINTER(TfFilterYuvControls), vp,
+                                                              C.POINTER(TfFilterYuv16Out)])
+        _proto(lib, "svtme_tf_filter_yuv_10bit", "restype", C.c_int32)
+        _proto(lib, "svtme_tf_window_yuv_10bit", "argtypes", [vp, C.POINTER(Job), C.c_uint32, C.c_uint32, C.c_uint32,
+                                                              C.POINTER(TfSubpelControls),
+                                                              C.POINTER(TfFilterYuvControls), C.c_uint64,
+                                                              C.POINTER(TfWindowOut), vp, C.c_uint32,
+                                                              C.POINTER(TfWindowYuv16Out)])
+        _proto(lib, "svtme_tf_window_yuv_10bit", "restype", C.c_int32)
         lib._svtme_protos = True
     return lib
 
@@ -1246,6 +1274,94 @@ class GpuME:
         if p16 is not None:
             res["plane16"] = p16
         return res
+
+    def attach_chroma_10bit(self, picture_number: int, cb: np.ndarray, cr: np.ndarray, width: int, height: int):
+        """svtme_picture_attach_chroma_10bit: attach full-precision 4:2:0 chroma (uint16, 0..1023) to the
+        resident picture; width x height is the luma size it was uploaded with."""
+        cb, cr = np.ascontiguousarray(cb, np.uint16), np.ascontiguousarray(cr, np.uint16)
+        shape = ((height + 1) >> 1, (width + 1) >> 1)
+        if cb.shape != shape or cr.shape != shape:
+            raise ValueError(f"chroma planes {cb.shape}, {cr.shape} for a {width}x{height} picture ({shape})")
+        self._check(self.lib.svtme_picture_attach_chroma_10bit(self.ctx, picture_number, cb.ctypes.data,
+                                                               cr.ctypes.data, shape[1], width, height),
+                    "svtme_picture_attach_chroma_10bit")
+
+    def download_chroma_10bit(self, picture_number: int, plane: int) -> np.ndarray:
+        """svtme_picture_download_chroma_10bit: plane 1 (Cb) or 2 (Cr) with its margins, (H/2 + 80,
+        W/2 + 80) u16."""
+        stride, w, h, pad = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32()
+        args = (C.byref(stride), C.byref(w), C.byref(h), C.byref(pad))
+        self._check(self.lib.svtme_picture_download_chroma_10bit(self.ctx, picture_number, plane, None, *args),
+                    "svtme_picture_download_chroma_10bit")
+        out = np.empty((h.value + 2 * pad.value, stride.value), np.uint16)
+        self._check(self.lib.svtme_picture_download_chroma_10bit(self.ctx, picture_number, plane, out.ctypes.data,
+                                                                 *args), "svtme_picture_download_chroma_10bit")
+        return out
+
+    def tf_filter_yuv_10bit(self, centre: int, refs, width: int, height: int, controls: TfFilterYuvControls,
+                            subpel: np.ndarray, with_err32: bool = True, want=("cb", "cr"), strides=None):
+        """svtme_tf_filter_yuv_10bit: tf_filter_10bit with the chroma stage -> (y [height, width], cb, cr
+        [(height + 1) >> 1, (width + 1) >> 1] u16 or None where not in `want`, err32 or None).
+        strides: (y, cb, cr) row distances in samples; the planes are then views of rows that far apart."""
+        n = len(refs)
+        sbs = sb_total(align8(width), align8(height))
+        subpel = np.ascontiguousarray(subpel, TF_SUBPEL_SB_DTYPE)
+        if subpel.size != n * sbs:
+            raise ValueError(f"{subpel.size} sub-pel results for {n} references x {sbs} SBs")
+        arr = (C.c_uint64 * max(n, 1))(*[int(r) for r in refs])
+        cw, ch = (width + 1) >> 1, (height + 1) >> 1
+        sy, scb, scr = strides or (width, cw, cw)
+        y = np.zeros((height, sy), np.uint16)
+        cb = np.zeros((ch, scb), np.uint16) if "cb" in want else None
+        cr = np.zeros((ch, scr), np.uint16) if "cr" in want else None
+        err32 = np.zeros((n, sbs, 4), np.uint32) if with_err32 else None
+        out = TfFilterYuv16Out(y=y.ctypes.data, cb=cb.ctypes.data if cb is not None else None,
+                               cr=cr.ctypes.data if cr is not None else None, y_stride=sy, cb_stride=scb,
+                               cr_stride=scr, err32=err32.ctypes.data if with_err32 else None)
+        self._check(self.lib.svtme_tf_filter_yuv_10bit(self.ctx, int(centre), arr, n, width, height,
+                                                       C.byref(controls), subpel.ctypes.data, C.byref(out)),
+                    "svtme_tf_filter_yuv_10bit")
+        return (y[:, :width], cb[:, :cw] if cb is not None else None, cr[:, :cw] if cr is not None else None,
+                err32)
+
+    def tf_window_yuv_10bit(self, jobs, src_w: int, src_h: int, subpel_controls: TfSubpelControls,
+                            filter_controls: TfFilterYuvControls, out_pn: int,
+                            want=("plane", "records", "subpel", "err32", "plane16", "cb", "cr"), uv_stride: int = None):
+        """svtme_tf_window_yuv_10bit: tf_window_10bit with the chroma stage; the result picture `out_pn`
+        gets the filtered 16-bit chroma planes too. -> {name: array} of the outputs named in `want`:
+        tf_window_10bit's, and cb, cr [(src_h + 1) >> 1, (src_w + 1) >> 1] u16."""
+        unknown = set(want) - {"plane", "records", "subpel", "err32", "plane16", "cb", "cr"}
+        if unknown:
+            raise ValueError(f"unknown outputs {sorted(unknown)}")
+        n = len(jobs)
+        arr = (Job * max(n, 1))(*jobs)
+        sbs = sb_total(align8(src_w), align8(src_h))
+        cw, ch = (src_w + 1) >> 1, (src_h + 1) >> 1
+        res, uv = {}, {}
+        if "plane" in want:
+            res["plane"] = np.zeros((src_h, src_w), np.uint8)
+        if "records" in want:
+            res["records"] = np.zeros((n, sbs), REF_RECORD_DTYPE)
+        if "subpel" in want:
+            res["subpel"] = np.zeros((n, sbs), TF_SUBPEL_SB_DTYPE)
+        if "err32" in want:
+            res["err32"] = np.zeros((n, sbs, 4), np.uint32)
+        p16 = np.zeros((src_h, src_w), np.uint16) if "plane16" in want else None
+        for name in ("cb", "cr"):
+            if name in want:
+                uv[name] = np.zeros((ch, cw), np.uint16)
+        us = cw if uv_stride is None else uv_stride
+        out = TfWindowOut(plane_stride=src_w, **{k: v.ctypes.data for k, v in res.items()})
+        out_uv = TfWindowYuv16Out(cb_stride=us, cr_stride=us, **{k: v.ctypes.data for k, v in uv.items()})
+        self._check(self.lib.svtme_tf_window_yuv_10bit(self.ctx, arr, n, src_w, src_h, C.byref(subpel_controls),
+                                                       C.byref(filter_controls), int(out_pn),
+                                                       C.byref(out) if res else None,
+                                                       p16.ctypes.data if p16 is not None else None, src_w,
+                                                       C.byref(out_uv) if uv else None),
+                    "svtme_tf_window_yuv_10bit")
+        if p16 is not None:
+            res["plane16"] = p16
+        return dict(res, **uv)
 
     def device_records(self):
         n = C.c_uint64()
