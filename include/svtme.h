@@ -953,6 +953,76 @@ svtme_status svtme_tf_window_yuv_10bit(svtme_ctx *ctx, const svtme_job *jobs, ui
                                        const svtme_tf_window_out *out, uint16_t *plane16, uint32_t plane16_stride,
                                        const svtme_tf_window_yuv16_out *out_uv);
 
+/* ---------------------------------------------------------------------------
+ * Low-delay temporal filtering: produce_temporally_filtered_pic_ld
+ * (temporal_filtering.c:3404-3816), what svt_av1_init_temporal_filtering runs with
+ * SVT_AV1_PRED_LOW_DELAY_B. No TF-ME and no sub-pel search: the prediction of every
+ * 64x64 block is the co-located block of the reference picture (MV (0, 0)), its
+ * 32x32 luma errors are VARIANCES (svt_aom_variance32x32_c / 32x16_c, at 10 bit
+ * svt_aom_highbd_10_variance*), and the weights are those of
+ * svt_av1_apply_zz_based_temporal_filter_planewise_medium[_hbd]_c: per 32x32 luma
+ * block and plane, (exp_tab[min(((var32 >> 2 (10 bit: >> 6)) << 2) /
+ * max(decay_fp16 >> 10, 1), 112)] * 1000) >> 17, 500 at the most, the chroma planes
+ * with the luma variance and their own decay factor. One fused kernel
+ * (svtme_tfld.hip) serves 8 and 10 bit, with and without 4:2:0 chroma.
+ * ------------------------------------------------------------------------- */
+typedef struct svtme_tf_ld_controls {
+    uint32_t tf_decay_factor_fp16[3]; /* MeContext.tf_decay_factor_fp16[C_Y / C_U / C_V], any value; [1], [2] ignored without chroma */
+    uint8_t sub_sampling_shift;       /* 0..1 */
+    uint8_t bit_depth;                /* 8 or 10 */
+    uint8_t chroma;                   /* 0: luma only; 1: tf_chroma, 4:2:0 */
+    uint8_t pad;                      /* 0 */
+} svtme_tf_ld_controls;               /* 16 bytes */
+
+typedef struct svtme_tf_ld_out {
+    void *y, *cb, *cr;                       /* uint8_t samples at 8 bit, uint16_t at 10 */
+    uint32_t y_stride, cb_stride, cr_stride; /* in samples */
+    uint32_t pad;
+    uint32_t *var32; /* NULL or n x SBs x 4: the 32x32 variances, SB raster order, quadrant = col + 2 * row */
+} svtme_tf_ld_out;   /* 48 bytes */
+#ifdef __cplusplus
+static_assert(sizeof(svtme_tf_ld_controls) == 16 && sizeof(svtme_tf_ld_out) == 48, "svtme_tf_ld layout");
+#else
+_Static_assert(sizeof(svtme_tf_ld_controls) == 16 && sizeof(svtme_tf_ld_out) == 48, "svtme_tf_ld layout");
+#endif
+
+/* The low-delay filter of one window of resident pictures into host memory: the
+ * counterpart of svtme_tf_filter / _yuv / _10bit / _yuv_10bit by controls->bit_depth
+ * and controls->chroma. width x height is the 8-aligned size the other TF calls
+ * take. At 8 bit the call reads level 0 of each picture and, with chroma, its
+ * attached 8-bit chroma; at 10 bit the attached 16-bit plane and, with chroma, the
+ * attached 16-bit chroma. out->y (required) receives x < width, y < height; out->cb
+ * and out->cr (optional, honoured only with chroma) the (width + 1) >> 1 by
+ * (height + 1) >> 1 chroma planes; out->var32 (optional) the variances. Synchronous;
+ * no resident picture is modified. Returns SVTME_ERR_BAD_PARAMETER before any GPU
+ * work for a NULL ctx / refs / controls / out / out->y, n outside
+ * 1..SVTME_MAX_BATCH_JOBS, a size that is not a non-zero multiple of 8 up to 16384,
+ * bit_depth not 8 or 10, chroma or sub_sampling_shift above 1, pad not 0, a stride
+ * under its plane's width, the centre among the references, and a picture that is
+ * not resident, has another size or lacks a plane the mode reads. */
+svtme_status svtme_tf_filter_ld(svtme_ctx *ctx, uint64_t centre_picture_number, const uint64_t *ref_picture_numbers,
+                                uint32_t n, uint32_t width, uint32_t height, const svtme_tf_ld_controls *controls,
+                                const svtme_tf_ld_out *out);
+
+/* The same window resident to resident: the counterpart of svtme_tf_window / _yuv /
+ * _10bit / _yuv_10bit, with no jobs (nothing is searched). src_width x src_height is
+ * the true size; the call aligns it to 8. The result picture out_picture_number is
+ * what the matching window call leaves by bit_depth and chroma: the filtered planes
+ * re-padded beyond the true size with their margins, levels 1 and 2 rebuilt, at 10
+ * bit level 0 = the 16-bit plane >> 2, and the attached planes of an older picture
+ * under that number kept or dropped as that call does. out_picture_number may be the
+ * centre's (in place) and may not be a reference's. `out` may be NULL; with no host
+ * copy asked for (NULL, or y, cb, cr and var32 all NULL) the call returns once the
+ * work is queued, and later readers of the result are ordered behind it on every
+ * lane. The host copies have the true size (chroma (src_width + 1) >> 1). Refusals:
+ * those of svtme_tf_filter_ld with a zero or oversized source size in place of the
+ * size rule, and the result number among the references; a refused call changes no
+ * picture. */
+svtme_status svtme_tf_window_ld(svtme_ctx *ctx, uint64_t centre_picture_number, const uint64_t *ref_picture_numbers,
+                                uint32_t n, uint32_t src_width, uint32_t src_height,
+                                const svtme_tf_ld_controls *controls, uint64_t out_picture_number,
+                                const svtme_tf_ld_out *out);
+
 /* Number of 64x64 SBs of a width x height picture, and R for a job. */
 uint32_t svtme_sb_total(uint32_t width, uint32_t height);
 uint32_t svtme_job_ref_slots(const svtme_job *job);

@@ -276,6 +276,23 @@ struct TffhcArgs {
     int32_t W, H;                                  // the 8-aligned luma size
 };
 
+// Arguments of the low-delay filter (svtme_tfld.hip: k_tfld), filled by the host. Every picture of a
+// window has the same geometry, so the sources are pointers to interior sample (0, 0) with one stride
+// per kind of plane. At 8 bit the luma planes are level 0 and the chroma planes the attached 8-bit
+// ones; at 10 bit the attached 16-bit planes. Strides are in bytes.
+struct TfldArgs {
+    const uint8_t *cen_y, *cen_c[2];                 // the centre picture (cen_c: with chroma)
+    const uint8_t *ref_y[SVTME_MAX_BATCH_JOBS];      // the references
+    const uint8_t *ref_c[2][SVTME_MAX_BATCH_JOBS];
+    int32_t y_stride, c_stride;
+    DevPlane dst_y, dst_c[2]; // a dense plane or the result picture's (may be the centre's); dst_c[p].base may be NULL
+    DevPlane dst8;            // 10 bit, the window call: the result picture's level 0; base NULL: none
+    uint32_t *var32;          // NULL or [n][sbs][4]
+    uint32_t decay[3], ss;    // svtme_tf_ld_controls
+    uint32_t n, sbs, pic_w_b64;
+    int32_t W, H; // the 8-aligned luma size
+};
+
 // Bytes per unit (one reference's SB) of the temporal filter's scratch sections, as svtme_tff.hip
 // indexes them; the host lays the sections out by these (TfScratch, svtme_windows.cpp).
 #define SVTME_TFF_TILE_BYTES 4096   // luma prediction: k_tff_pred / k_tff_norm, `A.tile + unit * 4096`

@@ -170,4 +170,7 @@ hipError_t svtme_launch_tffh_pic_yuv(const DevPlane *cen, const DevPlane *ref, u
                                      uint32_t height, const svtme_tf_filter_controls *ctl,
                                      const svtme_tf_subpel_sb *d_sub, uint16_t *d_tile, uint32_t *d_wgt, uint32_t *d_e32,
                                      const DevPlane *dst, const DevPlane *dst8, const TffhcArgs *U, hipStream_t s);
+// svtme_tfld.hip: the low-delay filter, one fused kernel; hbd: 16-bit planes, chroma: Cb and Cr too
+hipError_t svtme_prime_tfld(void);
+hipError_t svtme_launch_tfld(const TfldArgs *A, int hbd, int chroma, hipStream_t s);
 }

@@ -1,7 +1,7 @@
 // svtme_windows.cpp — the calls over a window of resident pictures, all on lane 0: the dynamic-GOP
 // detector (svtme_dg.hip) and temporal filtering's stages (svtme_tfsp.hip, svtme_tff.hip, svtme_tffh.hip,
 // svtme_tffhc.hip), alone
-// and as one window resident to resident. Each holds the context lock from its first launch to
+// and as one window resident to resident, and the low-delay filter (svtme_tfld.hip). Each holds the context lock from its first launch to
 // its last copy, as svtme_submit_picture does: the device outputs are the context's, and a
 // release / invalidate of a picture from another thread waits for the lock.
 #include <cstring>
@@ -607,4 +607,205 @@ extern "C" svtme_status svtme_tf_window_yuv_10bit(svtme_ctx *c, const svtme_job 
     const TfHbd hb    = {plane16, plane16_stride};
     return tf_window_impl("svtme_tf_window_yuv_10bit", &uv, &hb, c, jobs, n, src_width, src_height, sp_ctl, &f_ctl->luma,
                           out_pn, out);
+}
+
+// ----------------------------------------------------------------------------
+// Low-delay temporal filtering (svtme_tfld.hip): one fused kernel over the co-located blocks,
+// into dense planes for the host (svtme_tf_filter_ld) or into the result picture
+// (svtme_tf_window_ld), which is then re-padded and published as tf_window_impl's is.
+// ----------------------------------------------------------------------------
+// the checks of both calls that need no context; W x H: the 8-aligned size
+static svtme_status tf_ld_check(const char *fn, const svtme_ctx *c, uint64_t centre, const uint64_t *refs, uint32_t n,
+                                uint32_t W, uint32_t H, uint32_t out_w, const svtme_tf_ld_controls *ctl,
+                                const svtme_tf_ld_out *out) {
+    if (!c || !refs || !ctl)
+        return fail(SVTME_ERR_BAD_PARAMETER, "%s: null ctx, ref_picture_numbers or controls", fn);
+    if (n < 1 || n > SVTME_MAX_BATCH_JOBS)
+        return fail(SVTME_ERR_BAD_PARAMETER, "%s: %u references (1..%d)", fn, n, SVTME_MAX_BATCH_JOBS);
+    if (!W || !H || (W & 7) || (H & 7) || W > 16384 || H > 16384)
+        return fail(SVTME_ERR_BAD_PARAMETER, "%s: size %ux%u must be a non-zero multiple of 8, 16384 at the most", fn,
+                    W, H);
+    if ((ctl->bit_depth != 8 && ctl->bit_depth != 10) || ctl->chroma > 1 || ctl->sub_sampling_shift > 1 || ctl->pad)
+        return fail(SVTME_ERR_BAD_PARAMETER,
+                    "%s: controls out of range: bit_depth %u (8 or 10), chroma %u, sub_sampling_shift %u (0..1), "
+                    "pad %u (0)", fn, ctl->bit_depth, ctl->chroma, ctl->sub_sampling_shift, ctl->pad);
+    if (out && out->y && out->y_stride < out_w)
+        return fail(SVTME_ERR_BAD_PARAMETER, "%s: y_stride %u under the width %u", fn, out->y_stride, out_w);
+    if (out && ctl->chroma) {
+        const TfChroma uv = {{0, 0}, {(uint8_t *)out->cb, (uint8_t *)out->cr}, {out->cb_stride, out->cr_stride}};
+        const svtme_status st = chroma_strides_ok(fn, &uv, out_w);
+        if (st)
+            return st;
+    }
+    for (uint32_t k = 0; k < n; k++)
+        if (refs[k] == centre)
+            return fail(SVTME_ERR_BAD_PARAMETER, "%s: the centre picture %llu is reference %u", fn,
+                        (unsigned long long)centre, k);
+    return SVTME_OK;
+}
+
+// the kernel's sources: the planes the mode reads of the centre pb[0] and the n references behind it
+static void tfld_sources(TfldArgs &A, PicBuf *const *pb, uint32_t n, uint32_t W, uint32_t H,
+                         const svtme_tf_ld_controls *ctl) {
+    const bool hbd = ctl->bit_depth == 10;
+    auto luma      = [hbd](const PicBuf *p) -> const DevPlane & { return hbd ? p->hbd : p->pyr.lv[0]; };
+    auto chroma    = [hbd](const PicBuf *p, int pl) -> const DevPlane & { return hbd ? p->hchroma[pl] : p->chroma[pl]; };
+    A.cen_y        = luma(pb[0]).base;
+    A.y_stride     = luma(pb[0]).stride;
+    for (uint32_t k = 0; k < SVTME_MAX_BATCH_JOBS; k++) A.ref_y[k] = luma(pb[k < n ? k + 1 : 1]).base;
+    for (int p = 0; ctl->chroma && p < 2; p++) {
+        A.cen_c[p] = chroma(pb[0], p).base;
+        A.c_stride = chroma(pb[0], p).stride;
+        for (uint32_t k = 0; k < SVTME_MAX_BATCH_JOBS; k++) A.ref_c[p][k] = chroma(pb[k < n ? k + 1 : 1], p).base;
+    }
+    for (int p = 0; p < 3; p++) A.decay[p] = ctl->tf_decay_factor_fp16[p];
+    A.ss        = ctl->sub_sampling_shift;
+    A.n         = n;
+    A.pic_w_b64 = (W + 63) / 64;
+    A.sbs       = svtme_sb_total(W, H);
+    A.W         = (int32_t)W;
+    A.H         = (int32_t)H;
+}
+
+extern "C" svtme_status svtme_tf_filter_ld(svtme_ctx *c, uint64_t centre_picture_number,
+                                           const uint64_t *ref_picture_numbers, uint32_t n, uint32_t width,
+                                           uint32_t height, const svtme_tf_ld_controls *ctl, const svtme_tf_ld_out *out) {
+    const char *fn = "svtme_tf_filter_ld";
+    if (!out || !out->y)
+        return fail(SVTME_ERR_BAD_PARAMETER, "%s: null out or out->y", fn);
+    svtme_status st;
+    if ((st = tf_ld_check(fn, c, centre_picture_number, ref_picture_numbers, n, width, height, width, ctl, out)))
+        return st;
+    const uint32_t W = width, H = height, sbs = svtme_sb_total(W, H);
+    const bool hbd = ctl->bit_depth == 10, uv = ctl->chroma != 0;
+    uint64_t pn[SVTME_MAX_BATCH_JOBS + 1] = {centre_picture_number};
+    memcpy(pn + 1, ref_picture_numbers, n * sizeof(uint64_t));
+    std::lock_guard<std::mutex> lk(c->mu);
+    PicBuf *pb[SVTME_MAX_BATCH_JOBS + 1];
+    if ((st = resident_pics(c, fn, pn, n + 1, W, H, uv && !hbd, pb, hbd, uv && hbd)))
+        return st;
+    HIP_TRY(hipSetDevice(c->device));
+    // the scratch: the variances | the dense luma plane | Cb | Cr, rows of whole SBs (16-byte aligned sections)
+    const size_t bpp = hbd ? 2 : 1, pstride = (size_t)((W + 63) / 64) * 64;
+    const size_t var_bytes = sizeof(uint32_t) * 4 * (size_t)n * sbs, y_bytes = pstride * bpp * H;
+    const size_t c_bytes   = pstride / 2 * bpp * (H / 2);
+    if ((st = ensure_buf(&c->d_tff, &c->tff_cap, var_bytes + y_bytes + (uv ? 2 * c_bytes : 0))))
+        return st;
+    DevPlane ref[SVTME_MAX_BATCH_JOBS];
+    if ((st = join_window(c, pb, n, ref)))
+        return st;
+    uint8_t *base = (uint8_t *)c->d_tff;
+    TfldArgs A{};
+    tfld_sources(A, pb, n, W, H, ctl);
+    A.var32 = (uint32_t *)base;
+    A.dst_y = DevPlane{base + var_bytes, (int32_t)(pstride * bpp), (int32_t)W, (int32_t)H, 0};
+    void *const host_c[2]      = {out->cb, out->cr};
+    const uint32_t c_stride[2] = {out->cb_stride, out->cr_stride};
+    for (int p = 0; uv && p < 2; p++)
+        if (host_c[p])
+            A.dst_c[p] = DevPlane{base + var_bytes + y_bytes + p * c_bytes, (int32_t)(pstride / 2 * bpp), (int32_t)W / 2,
+                                  (int32_t)H / 2, 0};
+    Lane &L = c->lanes[0];
+    HIP_TRY(svtme_launch_tfld(&A, hbd, uv, L.s));
+    hipEvent_t done;
+    if ((st = submission_done(L, &done)))
+        return st;
+    mark_read(pb, n + 1, 0, done);
+    HIP_TRY(hipMemcpy2DAsync(out->y, out->y_stride * bpp, A.dst_y.base, pstride * bpp, W * bpp, H, hipMemcpyDeviceToHost,
+                             L.s));
+    for (int p = 0; uv && p < 2; p++)
+        if (host_c[p])
+            HIP_TRY(hipMemcpy2DAsync(host_c[p], c_stride[p] * bpp, A.dst_c[p].base, pstride / 2 * bpp, W / 2 * bpp, H / 2,
+                                     hipMemcpyDeviceToHost, L.s));
+    if (out->var32)
+        HIP_TRY(hipMemcpyAsync(out->var32, A.var32, var_bytes, hipMemcpyDeviceToHost, L.s));
+    HIP_TRY(hipStreamSynchronize(L.s));
+    return SVTME_OK;
+}
+
+extern "C" svtme_status svtme_tf_window_ld(svtme_ctx *c, uint64_t centre_picture_number,
+                                           const uint64_t *ref_picture_numbers, uint32_t n, uint32_t src_width,
+                                           uint32_t src_height, const svtme_tf_ld_controls *ctl, uint64_t out_pn,
+                                           const svtme_tf_ld_out *out) {
+    const char *fn = "svtme_tf_window_ld";
+    if (!src_width || !src_height || src_width > 16384 || src_height > 16384)
+        return fail(SVTME_ERR_BAD_PARAMETER, "%s: source size %ux%u (1..16384)", fn, src_width, src_height);
+    const uint32_t W = svtme_align8_u(src_width), H = svtme_align8_u(src_height), sbs = svtme_sb_total(W, H);
+    svtme_status st;
+    if ((st = tf_ld_check(fn, c, centre_picture_number, ref_picture_numbers, n, W, H, src_width, ctl, out)))
+        return st;
+    for (uint32_t k = 0; k < n; k++)
+        if (ref_picture_numbers[k] == out_pn)
+            return fail(SVTME_ERR_BAD_PARAMETER, "%s: the result picture %llu is reference %u", fn,
+                        (unsigned long long)out_pn, k);
+    const bool hbd = ctl->bit_depth == 10, uv = ctl->chroma != 0, uv8 = uv && !hbd, uv16 = uv && hbd;
+    uint64_t pn[SVTME_MAX_BATCH_JOBS + 1] = {centre_picture_number};
+    memcpy(pn + 1, ref_picture_numbers, n * sizeof(uint64_t));
+    std::lock_guard<std::mutex> lk(c->mu);
+    // (the pointers hold across the result picture's allocation, as in tf_window_impl)
+    PicBuf *pb[SVTME_MAX_BATCH_JOBS + 1];
+    if ((st = resident_pics(c, fn, pn, n + 1, W, H, uv8, pb, hbd, uv16)))
+        return st;
+    HIP_TRY(hipSetDevice(c->device));
+    const bool want_var = out && out->var32;
+    const size_t var_bytes = sizeof(uint32_t) * 4 * (size_t)n * sbs;
+    if (want_var && (st = ensure_buf(&c->d_tff, &c->tff_cap, var_bytes)))
+        return st;
+    DevPlane ref[SVTME_MAX_BATCH_JOBS];
+    if ((st = join_window(c, pb, n, ref)))
+        return st;
+    PicBuf *po;
+    if ((st = alloc_pic(c, out_pn, W, H, &po, uv8, hbd, uv16)) || (uv8 && (st = alloc_chroma(c, *po))) ||
+        (hbd && (st = alloc_hbd(c, *po))) || (uv16 && (st = alloc_hbd_chroma(c, *po))))
+        return st;
+    Lane &L = c->lanes[0];
+    // its old planes, if it had any: an upload still running, readers queued on the other lanes
+    if ((st = join_upload(c, *po, 0)) || (st = after_readers(c, *po, L.s)))
+        return st;
+    TfldArgs A{};
+    tfld_sources(A, pb, n, W, H, ctl);
+    A.var32 = want_var ? (uint32_t *)c->d_tff : nullptr;
+    A.dst_y = hbd ? po->hbd : po->pyr.lv[0];
+    if (hbd)
+        A.dst8 = po->pyr.lv[0];
+    for (int p = 0; uv && p < 2; p++) A.dst_c[p] = hbd ? po->hchroma[p] : po->chroma[p];
+    HIP_TRY(svtme_launch_tfld(&A, hbd, uv, L.s));
+    // beyond the true sizes and the margins, each plane from its own interior; then levels 1 and 2
+    if (hbd && (st = build_hbd(po, (const uint16_t *)po->hbd.base, (uint32_t)po->hbd.stride / 2, src_width, src_height, L.s)))
+        return st;
+    for (int p = 0; uv16 && p < 2; p++)
+        if ((st = build_hbd_chroma(po, p, (const uint16_t *)po->hchroma[p].base, (uint32_t)po->hchroma[p].stride / 2,
+                                   (src_width + 1) >> 1, (src_height + 1) >> 1, L.s)))
+            return st;
+    if ((st = build_pyramid(c, po, po->pyr.lv[0].base, (uint32_t)po->pyr.lv[0].stride, src_width, src_height, 0, L.s)))
+        return st;
+    for (int p = 0; uv8 && p < 2; p++)
+        if ((st = build_chroma(po, p, po->chroma[p].base, (uint32_t)po->chroma[p].stride, (src_width + 1) >> 1,
+                               (src_height + 1) >> 1, L.s)))
+            return st;
+    hipEvent_t done;
+    if ((st = submission_done(L, &done)))
+        return st;
+    mark_read(pb, n + 1, 0, done);
+    po->used[0] = done; // a later upload under its number waits for the window
+    if (!po->ready)
+        HIP_TRY(hipEventCreateWithFlags(&po->ready, hipEventDisableTiming));
+    if ((st = upload_publish(*po, L.s, kAllLanes & ~1u)))
+        return st;
+    if (!out || (!out->y && !(uv && (out->cb || out->cr)) && !out->var32))
+        return SVTME_OK;
+    const size_t bpp = hbd ? 2 : 1;
+    if (out->y)
+        HIP_TRY(hipMemcpy2DAsync(out->y, out->y_stride * bpp, A.dst_y.base, (size_t)A.dst_y.stride, src_width * bpp,
+                                 src_height, hipMemcpyDeviceToHost, L.s));
+    void *const host_c[2]      = {out->cb, out->cr};
+    const uint32_t c_stride[2] = {out->cb_stride, out->cr_stride};
+    for (int p = 0; uv && p < 2; p++)
+        if (host_c[p])
+            HIP_TRY(hipMemcpy2DAsync(host_c[p], c_stride[p] * bpp, A.dst_c[p].base, (size_t)A.dst_c[p].stride,
+                                     ((src_width + 1) >> 1) * bpp, (src_height + 1) >> 1, hipMemcpyDeviceToHost, L.s));
+    if (want_var)
+        HIP_TRY(hipMemcpyAsync(out->var32, A.var32, var_bytes, hipMemcpyDeviceToHost, L.s));
+    HIP_TRY(hipStreamSynchronize(L.s));
+    return SVTME_OK;
 }

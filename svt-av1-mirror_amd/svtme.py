@@ -325,6 +325,31 @@ class TfWindowYuv16Out(C.Structure):
     _fields_ = [("cb", C.c_void_p), ("cr", C.c_void_p), ("cb_stride", C.c_uint32), ("cr_stride", C.c_uint32)]
 
 
+class TfLdControls(C.Structure):
+    """svtme_tf_ld_controls: the low-delay filter's decay factors (Y, Cb, Cr), sub-sampling shift, bit depth
+    (8 or 10) and whether chroma is filtered."""
+    _fields_ = [("tf_decay_factor_fp16", C.c_uint32 * 3), ("sub_sampling_shift", C.c_uint8), ("bit_depth", C.c_uint8),
+                ("chroma", C.c_uint8), ("pad", C.c_uint8)]
+
+    @staticmethod
+    def from_dict(d: dict) -> "TfLdControls":
+        return TfLdControls(tf_decay_factor_fp16=(C.c_uint32 * 3)(*[int(v) for v in d["tf_decay_factor_fp16"]]),
+                            sub_sampling_shift=int(d["sub_sampling_shift"]), bit_depth=int(d["bit_depth"]),
+                            chroma=int(d["chroma"]), pad=int(d.get("pad", 0)))
+
+    def as_dict(self) -> dict:
+        return {"tf_decay_factor_fp16": [int(v) for v in self.tf_decay_factor_fp16],
+                "sub_sampling_shift": int(self.sub_sampling_shift), "bit_depth": int(self.bit_depth),
+                "chroma": int(self.chroma)}
+
+
+class TfLdOut(C.Structure):
+    """svtme_tf_ld_out: where the low-delay calls write, strides in samples (u8 at 8 bit, u16 at 10); cb, cr and
+    var32 may be NULL, in the window call y too."""
+    _fields_ = [("y", C.c_void_p), ("cb", C.c_void_p), ("cr", C.c_void_p), ("y_stride", C.c_uint32),
+                ("cb_stride", C.c_uint32), ("cr_stride", C.c_uint32), ("pad", C.c_uint32), ("var32", C.c_void_p)]
+
+
 TAIL_BYTES = 24  # svtme_record_tail: the last 24 bytes of svtme_ref_record
 
 
@@ -820,6 +845,13 @@ def _job_api_protos(lib):
                                                               C.POINTER(TfWindowOut), vp, C.c_uint32,
                                                               C.POINTER(TfWindowYuv16Out)])
         _proto(lib, "svtme_tf_window_yuv_10bit", "restype", C.c_int32)
+        _proto(lib, "svtme_tf_filter_ld", "argtypes", [vp, C.c_uint64, C.POINTER(C.c_uint64), C.c_uint32, C.c_uint32,
+                                                       C.c_uint32, C.POINTER(TfLdControls), C.POINTER(TfLdOut)])
+        _proto(lib, "svtme_tf_filter_ld", "restype", C.c_int32)
+        _proto(lib, "svtme_tf_window_ld", "argtypes", [vp, C.c_uint64, C.POINTER(C.c_uint64), C.c_uint32, C.c_uint32,
+                                                       C.c_uint32, C.POINTER(TfLdControls), C.c_uint64,
+                                                       C.POINTER(TfLdOut)])
+        _proto(lib, "svtme_tf_window_ld", "restype", C.c_int32)
         lib._svtme_protos = True
     return lib
 
@@ -1362,6 +1394,61 @@ class GpuME:
         if p16 is not None:
             res["plane16"] = p16
         return dict(res, **uv)
+
+    def _tf_ld_out(self, controls: TfLdControls, n: int, w: int, h: int, want, strides):
+        """The host buffers of a low-delay call for the outputs named in `want` -> (TfLdOut, {name: array})."""
+        unknown = set(want) - {"y", "cb", "cr", "var32"}
+        if unknown:
+            raise ValueError(f"unknown outputs {sorted(unknown)}")
+        dt = np.uint16 if controls.bit_depth == 10 else np.uint8
+        cw, ch = (w + 1) >> 1, (h + 1) >> 1
+        sy, scb, scr = strides or (w, cw, cw)
+        bufs = {}
+        if "y" in want:
+            bufs["y"] = np.zeros((h, sy), dt)
+        if "cb" in want:
+            bufs["cb"] = np.zeros((ch, scb), dt)
+        if "cr" in want:
+            bufs["cr"] = np.zeros((ch, scr), dt)
+        if "var32" in want:
+            bufs["var32"] = np.zeros((n, sb_total(align8(w), align8(h)), 4), np.uint32)
+        out = TfLdOut(y_stride=sy, cb_stride=scb, cr_stride=scr, **{k: v.ctypes.data for k, v in bufs.items()})
+        return out, bufs
+
+    @staticmethod
+    def _tf_ld_views(bufs: dict, w: int) -> dict:
+        cw = (w + 1) >> 1
+        return {k: (v if k == "var32" else v[:, :w if k == "y" else cw]) for k, v in bufs.items()}
+
+    def tf_filter_ld(self, centre: int, refs, width: int, height: int, controls: TfLdControls,
+                     want=("y", "cb", "cr", "var32"), strides=None) -> dict:
+        """svtme_tf_filter_ld: the low-delay temporal filter (co-located prediction, variance-based
+        weights) of resident pictures -> {name: array} of the outputs named in `want`: y [height, width],
+        cb, cr [(height + 1) >> 1, (width + 1) >> 1] (u8 at 8 bit, u16 at 10; only with controls.chroma),
+        var32 [refs, SBs, 4]. strides: (y, cb, cr) row distances in samples; the planes are then views
+        of rows that far apart. width x height is the 8-aligned size."""
+        n = len(refs)
+        arr = (C.c_uint64 * max(n, 1))(*[int(r) for r in refs])
+        if not controls.chroma:
+            want = [k for k in want if k not in ("cb", "cr")]
+        out, bufs = self._tf_ld_out(controls, n, width, height, want, strides)
+        self._check(self.lib.svtme_tf_filter_ld(self.ctx, int(centre), arr, n, width, height, C.byref(controls),
+                                                C.byref(out)), "svtme_tf_filter_ld")
+        return self._tf_ld_views(bufs, width)
+
+    def tf_window_ld(self, centre: int, refs, src_w: int, src_h: int, controls: TfLdControls, out_pn: int,
+                     want=(), strides=None) -> dict:
+        """svtme_tf_window_ld: the same window resident to resident; the result picture `out_pn` (it may
+        be `centre`) is what the matching svtme_tf_window* call leaves. -> {name: array} of the host
+        copies named in `want` (y, cb, cr at the true size, var32); with none the call only queues."""
+        n = len(refs)
+        arr = (C.c_uint64 * max(n, 1))(*[int(r) for r in refs])
+        if not controls.chroma:
+            want = [k for k in want if k not in ("cb", "cr")]
+        out, bufs = self._tf_ld_out(controls, n, src_w, src_h, want, strides)
+        self._check(self.lib.svtme_tf_window_ld(self.ctx, int(centre), arr, n, src_w, src_h, C.byref(controls),
+                                                int(out_pn), C.byref(out) if bufs else None), "svtme_tf_window_ld")
+        return self._tf_ld_views(bufs, src_w)
 
     def device_records(self):
         n = C.c_uint64()
