@@ -375,7 +375,7 @@ extern "C" svtme_status svtme_picture_upload(svtme_ctx *c, uint64_t pn, const ui
 
 extern "C" svtme_status svtme_picture_upload_10bit(svtme_ctx *c, uint64_t pn, const uint16_t *y, uint32_t stride,
                                                    uint32_t w, uint32_t h) {
-    return upload_sync("svtme_picture_upload", c, pn, y, stride, w, h, 1, false);
+    return upload_sync("svtme_picture_upload_10bit", c, pn, y, stride, w, h, 1, false);
 }
 
 extern "C" svtme_status svtme_picture_upload_device(svtme_ctx *c, uint64_t pn, const uint8_t *d_y, uint32_t stride,
@@ -398,7 +398,7 @@ extern "C" svtme_status svtme_picture_invalidate(svtme_ctx *c, uint64_t pn, cons
                         (unsigned long long)pn, pb->W, pb->H, w, h);
     }
     // same stream as the jobs: the rebuild runs after every job already queued
-    return upload_sync("svtme_picture_upload", c, pn, y, stride, w, h, 0, false);
+    return upload_sync("svtme_picture_invalidate", c, pn, y, stride, w, h, 0, false);
 }
 
 // ---- asynchronous 8-bit uploads ----
@@ -529,10 +529,10 @@ extern "C" svtme_status svtme_picture_upload_copy_async(svtme_ctx *c, uint64_t p
             }
             return u != nullptr;
         });
+        if (!u->done) // before the slot is taken: a failure here leaves it free
+            HIP_TRY(hipEventCreateWithFlags(&u->done, hipEventDisableTiming));
         c->up_next = (uint32_t)(u - c->up + 1) % SVTME_UPLOAD_SLOTS;
         u->busy    = true;
-        if (!u->done)
-            HIP_TRY(hipEventCreateWithFlags(&u->done, hipEventDisableTiming));
     }
     // outside the context lock: other threads submit jobs meanwhile
     const size_t need = (size_t)w * h;

@@ -259,3 +259,326 @@ def test_dg_bad_arguments(svtme, gpu):
     finally:
         for t in (6, 8, 106, 108):
             gpu.release(BASE + t)
+
+
+# ============================================================================
+# The kernel against an independent model (tests/dg_model.py) away from the fixture shapes
+# ============================================================================
+import functools  # noqa: E402
+import itertools  # noqa: E402
+
+import dg_model as DM  # noqa: E402
+import pyramid_model as PM  # noqa: E402
+
+MODEL = DM.DgModel()
+SWEEP_SIZES = [(8, 8), (64, 64), (136, 72), (121, 67), (200, 136)]
+BIG = (576, 520)  # the smallest picture class in which an interior SB gets the whole 128 x 128 window
+SWEEP_AREAS = [(8, 8), (16, 16), (20, 12), (64, 64), (128, 128), (128, 1), (8, 121), (40, 7)]
+CONTENTS = ("ramp++", "ramp+-", "ramp-+", "ramp--", "noise", "same", "sat", "flat", "tile", "tile_skew", "thr")
+SWEEP_SEED, SWEEP_DRAWS = 4242, 118  # the coverage test passes from 19 draws on; 120 detector calls
+
+
+def content(kind: str, w: int, h: int, seed: int = 0):
+    """-> (cur, ref), (h, w) uint8 each. Values are constant over 4x4 blocks where the sixteenth plane is
+    to hold chosen values exactly (the 2x2 means of equal samples are the samples)."""
+    rng = np.random.default_rng([w, h, seed, CONTENTS.index(kind)])
+    X, Y = np.meshgrid(np.arange(w) // 4, np.arange(h) // 4)
+    if kind.startswith("ramp"):
+        # flat zero against a ramp of 3 per sixteenth sample: the SAD is least in one corner of every window
+        gx = X if kind[4] == "+" else X.max() - X
+        gy = Y if kind[5] == "+" else Y.max() - Y
+        ref = 3 * (gx + gy)
+        assert ref.max() <= 255
+        return np.zeros((h, w), np.uint8), ref.astype(np.uint8)
+    if kind == "noise":
+        return rng.integers(0, 256, (h, w), dtype=np.uint8), rng.integers(0, 256, (h, w), dtype=np.uint8)
+    if kind == "same":
+        cur = rng.integers(0, 256, (h, w), dtype=np.uint8)
+        return cur, cur.copy()
+    if kind == "sat":
+        return np.zeros((h, w), np.uint8), np.full((h, w), 255, np.uint8)
+    if kind == "flat":
+        return np.full((h, w), 128, np.uint8), np.full((h, w), 128, np.uint8)
+    if kind in ("tile", "tile_skew"):
+        # a sixteenth-resolution tile repeated: equal minima a chosen number of rows and columns apart;
+        # skewed, row y of the tile is row 0 rotated by 5 y, so the minima of later rows lie in earlier columns
+        if kind == "tile":
+            T = rng.integers(0, 256, (9, 12), dtype=np.uint8)
+        else:
+            row = rng.integers(0, 256, 16, dtype=np.uint8)
+            T = np.stack([np.roll(row, -5 * y) for y in range(16)])
+        six = np.tile(T, (h // 4 // T.shape[0] + 2, w // 4 // T.shape[1] + 2))
+        pic = np.kron(six, np.ones((4, 4), np.uint8))[:h, :w]
+        return pic, pic.copy()
+    if kind == "thr":
+        # SADs of exactly 16 * 16 * 30 and, in the SB whose block holds the one sample at 31, one more
+        cur = np.full((h, w), 30, np.uint8)
+        cur[20:24, 20:24] = 31
+        return cur, np.zeros((h, w), np.uint8)
+    raise ValueError(kind)
+
+
+def sweep_list(draws: int):
+    """(size, area, content kind): two calls at BIG, then the first `draws` of a seeded shuffle of
+    SWEEP_SIZES x SWEEP_AREAS x CONTENTS."""
+    rng = np.random.default_rng(SWEEP_SEED)
+    every = list(itertools.product(SWEEP_SIZES, SWEEP_AREAS, CONTENTS))
+    return [(BIG, (128, 128), "noise"), (BIG, (128, 128), "tile_skew")] + \
+        [every[i] for i in rng.permutation(len(every))[:draws]]
+
+
+@functools.lru_cache(maxsize=None)
+def expected(size, area, kind):
+    """The model's (per-SB results, metrics, per-SB events) of one sweep entry; computed once."""
+    cur, ref = content(kind, *size)
+    events = []
+    sb, met = MODEL.detect(cur, ref, *area, events=events)
+    sb.setflags(write=False)
+    return sb, tuple(met), tuple(events)
+
+
+def coverage_items(entries) -> dict:
+    """{item: reached}: conditions on the inputs, from the model alone."""
+    ev = [e for entry in entries for e in expected(*entry)[2]]
+    mets = [expected(*entry)[1] for entry in entries]
+
+    def some(f):
+        return any(f(e) for e in ev)
+
+    got = {
+        "winner at (0, 0)": some(lambda e: e["win_x"] == 0 and e["win_y"] == 0 and e["n_pos"] > 1),
+        "winner in the last column": some(lambda e: e["win_x"] == e["sw"] - 1 and e["sw"] > 1),
+        "winner in the last row": some(lambda e: e["win_y"] == e["sh"] - 1 and e["sh"] > 1),
+        "winner at (sw - 1, sh - 1)": some(lambda e: e["win_x"] == e["sw"] - 1 and e["win_y"] == e["sh"] - 1 and
+                                           e["sw"] > 1 and e["sh"] > 1),
+        "minima 8 or more rows apart": some(lambda e: 2 <= e["n_min"] < e["n_pos"] and e["min_row_span"] >= 8),
+        "minima 4 or more columns apart, the earlier row in the later column":
+            some(lambda e: e["n_min"] < e["n_pos"] and e["min_skew"]),
+        "every position ties": some(lambda e: e["n_min"] == e["n_pos"] and e["n_pos"] > 1),
+        "sw of 8 that is no multiple of 16": some(lambda e: e["sw"] % 8 == 0 and e["sw"] % 16 != 0),
+        "sh of 1": some(lambda e: e["sh"] == 1),
+        "sh no multiple of 8": some(lambda e: e["sh"] % 8 != 0 and e["sh"] > 8),
+        "sh of 128": some(lambda e: e["sh"] == 128),
+        "x0 & 3 of 0": some(lambda e: e["x0_and_3"] == 0),
+        "x0 & 3 of 1": some(lambda e: e["x0_and_3"] == 1),
+        "clamped at both sides": some(lambda e: e["clamped"][0] and e["clamped"][1]),
+        "clamped above and below": some(lambda e: e["clamped"][2] and e["clamped"][3]),
+        "negative sum_in_vectors": any(m[3] < 0 for m in mets),
+    }
+    for sw in (6, 8, 16, 24, 128):
+        got[f"sw of {sw}"] = some(lambda e: e["sw"] == sw)
+    for k, side in enumerate(("left", "right", "top", "bottom")):
+        got[f"clamped at the {side}"] = some(lambda e: e["clamped"][k])
+    for sad in (0, 65280, DM.CPLX_TH, DM.CPLX_TH + 1):
+        got[f"SAD of {sad}"] = some(lambda e: e["min_sad"] == sad)
+    for axis in ("mv_x", "mv_y"):
+        got[f"negative {axis}"] = some(lambda e: e[axis] < 0)
+        got[f"zero {axis}"] = some(lambda e: e[axis] == 0)
+        got[f"positive {axis}"] = some(lambda e: e[axis] > 0)
+    return got
+
+
+SWEEP = sweep_list(SWEEP_DRAWS)
+
+
+def entry_id(entry):
+    (w, h), (sa_w, sa_h), kind = entry
+    return f"{w}x{h}-sa{sa_w}x{sa_h}-{kind}"
+
+
+# ----------------------------------------------------------------------------
+# CPU: the model against the fixtures, the generator and svtme_dg_reduce; what the sweep reaches
+# ----------------------------------------------------------------------------
+def test_dg_model_is_a_second_restatement():
+    src = open(DM.__file__).read()
+    assert "import make_golden_dg" not in src and "import svtme" not in src and DM.METRIC_FIELDS == G.METRIC_FIELDS
+    assert DM.SB_DTYPE == G.S.DG_SB_DTYPE
+
+
+@pytest.mark.parametrize("case", DG_CASES, ids=lambda c: c["id"])
+def test_dg_model_equals_fixture(gold, case):
+    frames = G.case_frames(case)
+    for k, (cur, ref) in enumerate(case["pairs"]):
+        sb, met = MODEL.detect(frames[cur], frames[ref], *case["sa"])
+        want = gold[case["id"] + ".sb"][k]
+        for f in ("sad", "mv_x", "mv_y"):
+            bad = np.flatnonzero(sb[f] != want[f])
+            assert bad.size == 0, (case["id"], k, f, int(bad[0]), sb[bad[0]], want[bad[0]])
+        assert met == gold[case["id"] + ".metrics"][k].tolist(), (case["id"], k)
+
+
+def test_dg_model_windows_equal_generator():
+    for (w, h) in SWEEP_SIZES + [BIG]:
+        for sa in SWEEP_AREAS:
+            assert [win[:6] for win in MODEL.sb_windows(w, h, *sa)] == G.sb_windows(w, h, *sa), (w, h, sa)
+
+
+def test_dg_reduce_equals_model_on_random_arrays(svtme):
+    """svtme_dg_reduce (product host code) against the model's metrics. perc_active and perc_cplx are
+    count * 100 / n with count <= n, at most 100: the uint8_t narrowing never changes them, so no input
+    can need the & 0xFF; the arrays reach 100 instead."""
+    rng = np.random.default_rng(99)
+    hit = set()
+    for wb, hb in ((1, 1), (1, 2), (2, 1), (3, 2), (4, 4), (9, 9)):
+        n = wb * hb
+        for rep in range(12):
+            w, h = 64 * wb - int(rng.integers(0, 56)), 64 * hb - int(rng.integers(0, 56))
+            sb = np.zeros(n, svtme.DG_SB_DTYPE)
+            sb["sad"] = rng.choice([0, DM.CPLX_TH, DM.CPLX_TH + 1, 65280, int(rng.integers(0, 65281))], n)
+            sb["mv_x"] = rng.integers(-128, 128, n) * 4 * rng.integers(0, 2, n)
+            sb["mv_y"] = rng.integers(-128, 128, n) * 4 * rng.integers(0, 2, n)
+            if rep == 0:  # every vector points inwards
+                bx, by = np.arange(n) % wb, np.arange(n) // wb
+                sb["mv_x"] = np.where(bx < wb // 2, 4, -4)
+                sb["mv_y"] = np.where(by < hb // 2, 8, -8)
+            if rep == 1:  # one inward vector
+                sb["mv_x"], sb["mv_y"] = 0, 0
+                sb["mv_x"][0] = 4
+            want = MODEL.metrics(w, h, sb)
+            assert metrics_rows([svtme.dg_reduce(w, h, sb)])[0] == want, (wb, hb, rep, sb)
+            hit |= {("sad", int(s)) for s in sb["sad"] if s in (DM.CPLX_TH, DM.CPLX_TH + 1)}
+            if want[3] < 0 and (want[3] * 100) % n:
+                hit.add("negative, not whole")
+                assert want[4] == -((-want[3] * 100) // n) != (want[3] * 100) // n
+            if want[6] == 100:
+                hit.add("all active")
+    assert hit == {("sad", DM.CPLX_TH), ("sad", DM.CPLX_TH + 1), "negative, not whole", "all active"}
+
+
+def test_dg_sweep_coverage():
+    assert len(SWEEP) == len(set(SWEEP)) <= 150 and sum(e[0] == BIG for e in SWEEP) <= 2
+    assert {e[0] for e in SWEEP} == set(SWEEP_SIZES + [BIG]) and {e[1] for e in SWEEP} == set(SWEEP_AREAS)
+    assert {e[2] for e in SWEEP} == set(CONTENTS)
+    missing = [k for k, v in coverage_items(SWEEP).items() if not v]
+    assert not missing, missing
+
+
+PYRAMID_VARIANTS = {"round with +1": dict(rnd=1), "round with +0": dict(rnd=0), "zero margins": dict(margin="constant"),
+                    "pad to 8 by zeros": dict(pad8="constant"), "quarter from the padded plane, shifted": dict(quarter_shift=1)}
+DG_VARIANTS = {"the last minimum wins": dict(first_wins=False), "x-major order": dict(y_major=False),
+               "no & ~7 on the width": dict(width_mult8=False),
+               "area reduced when the left clamp moves the origin": dict(reduce_on_left_clamp=True),
+               "padding 16": dict(pad=16), ">= at the complexity threshold": dict(cplx_strict=False),
+               "floor division": dict(trunc_div=False)}
+
+
+def differs(entry, model=MODEL, pyramid=PM.pyramid) -> bool:
+    sb, met = model.detect(*content(entry[2], *entry[0]), *entry[1], pyramid=pyramid)
+    want_sb, want_met, _ = expected(*entry)
+    return sb.tobytes() != want_sb.tobytes() or met != list(want_met)
+
+
+@pytest.mark.parametrize("name", list(PYRAMID_VARIANTS) + list(DG_VARIANTS))
+def test_dg_sweep_discriminates(name):
+    """A deliberately wrong model changes at least one expected value of the sweep: the inputs can tell."""
+    small = [e for e in SWEEP if e[0] != BIG]
+    assert not any(differs(e) for e in small[:5])  # (the model itself does not)
+    if name in PYRAMID_VARIANTS:
+        wrong = functools.partial(PM.pyramid, **PYRAMID_VARIANTS[name])
+        assert any(differs(e, pyramid=wrong) for e in small), name
+    else:
+        wrong = type("WrongDg", (DM.DgModel,), DG_VARIANTS[name])()
+        assert any(differs(e, model=wrong) for e in small), name
+
+
+# ----------------------------------------------------------------------------
+# GPU: svtme_dg_detect against the model
+# ----------------------------------------------------------------------------
+def assert_equal_to_model(mets, sb, k, want_sb, want_met, what):
+    if sb is not None:
+        for f in ("sad", "mv_x", "mv_y"):
+            bad = np.flatnonzero(sb[k][f] != want_sb[f])
+            assert bad.size == 0, (what, f, "SB", int(bad[0]), sb[k][bad[0]], want_sb[bad[0]], len(bad))
+    assert metrics_rows([mets[k]])[0] == list(want_met), what
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("entry", SWEEP, ids=entry_id)
+def test_dg_sweep_equals_model(svtme, gpu, entry):
+    size, area, kind = entry
+    cur, ref = content(kind, *size)
+    want_sb, want_met, _ = expected(*entry)
+    gpu.upload(BASE + 201, cur)
+    gpu.upload(BASE + 202, ref)
+    try:
+        mets, sb = gpu.dg_detect([(BASE + 201, BASE + 202)], *area)
+        assert sb.shape == (1, len(want_sb))
+        assert_equal_to_model(mets, sb, 0, want_sb, want_met, entry)
+        mets2, none = gpu.dg_detect([(BASE + 201, BASE + 202)], *area, with_sb=False)
+        assert none is None
+        assert_equal_to_model(mets2, None, 0, want_sb, want_met, entry)
+    finally:
+        gpu.release(BASE + 201)
+        gpu.release(BASE + 202)
+
+
+@pytest.mark.gpu
+def test_dg_full_batch_of_mixed_contents(svtme, gpu):
+    """SVTME_DG_MAX_PAIRS pairs of mixed contents in one call equal the single calls and the model;
+    one pair searches a picture against itself."""
+    size, area = (136, 72), (64, 64)
+    kinds = ("noise", "ramp+-", "sat", "same", "tile_skew", "thr", "flat", "ramp--")
+    assert len(kinds) == svtme.DG_MAX_PAIRS == 8
+    pairs, used = [], []
+    for k, kind in enumerate(kinds):
+        cur, ref = content(kind, *size)
+        c, r = BASE + 300 + 2 * k, BASE + 301 + 2 * k
+        gpu.upload(c, cur)
+        used.append(c)
+        if kind == "same":
+            r = c  # cur == ref: one resident picture
+        else:
+            gpu.upload(r, ref)
+            used.append(r)
+        pairs.append((c, r))
+    try:
+        mets, sb = gpu.dg_detect(pairs, *area)
+        for k, kind in enumerate(kinds):
+            want_sb, want_met, _ = expected(size, area, kind)
+            assert_equal_to_model(mets, sb, k, want_sb, want_met, kind)
+            m1, sb1 = gpu.dg_detect([pairs[k]], *area)
+            assert sb1.tobytes() == sb[k:k + 1].tobytes() and metrics_rows(m1) == metrics_rows(mets[k:k + 1]), kind
+    finally:
+        for pn in used:
+            gpu.release(pn)
+
+
+@pytest.mark.gpu
+def test_dg_10bit_pair_equals_model_on_msb_planes(svtme, gpu):
+    w, h, area = 121, 67, (64, 64)
+    rng = np.random.default_rng(10)
+    cur, ref = (rng.integers(0, 1024, (h, w), dtype=np.uint16) for _ in range(2))
+    want_sb, want_met = MODEL.detect(cur, ref, *area)
+    assert want_sb.tobytes() == MODEL.detect((cur >> 2).astype(np.uint8), (ref >> 2).astype(np.uint8), *area)[0].tobytes()
+    gpu.upload(BASE + 401, cur)  # svtme_picture_upload_10bit
+    gpu.upload(BASE + 402, ref)
+    try:
+        mets, sb = gpu.dg_detect([(BASE + 401, BASE + 402)], *area)
+        assert_equal_to_model(mets, sb, 0, want_sb, want_met, "10 bit")
+    finally:
+        gpu.release(BASE + 401)
+        gpu.release(BASE + 402)
+
+
+@pytest.mark.gpu
+def test_dg_after_device_async_upload_equals_model(svtme, gpu):
+    """Both pictures through svtme_picture_upload_device_async and no sync: the call waits on the GPU."""
+    import torch
+
+    size, area, kind = (200, 136), (128, 128), "noise"
+    w, h = size
+    stride, off = w + 13, 3
+    want_sb, want_met, _ = expected(size, area, kind)
+    keep = []
+    for pic in content(kind, w, h):
+        buf = np.full(off + stride * h, 0xA5, np.uint8)
+        buf[off:].reshape(h, stride)[:, :w] = pic
+        keep.append(torch.from_numpy(buf).cuda())
+    torch.cuda.synchronize()  # the planes are on the device before the upload stream reads them
+    for k, t in enumerate(keep):
+        gpu.upload_device_async(BASE + 501 + k, t.data_ptr() + off, stride, w, h)
+    mets, sb = gpu.dg_detect([(BASE + 501, BASE + 502)], *area)
+    for k in range(2):
+        assert gpu.lib.svtme_picture_release(gpu.ctx, BASE + 501 + k) == 0
+    gpu.sync()
+    assert_equal_to_model(mets, sb, 0, want_sb, want_met, "device async")
