@@ -191,7 +191,7 @@ typedef struct svtme_ref_record {
     uint8_t searched;    /* do_ref when the integer search ran */
     uint8_t do_ref;      /* final do_ref */
     uint8_t tf_early_exit; /* MCTF only: HME-only exit taken (tf_use_pred_64x64_only_th = ~0, :3111) */
-    uint8_t pad[5];
+    uint8_t pad[5];        /* pad bytes are zero: every kernel path writes whole 704-byte records */
 } svtme_ref_record; /* 704 bytes */
 
 /* Per SB candidate list + distortions (MeSbResults, me_sb_results.h:44, and the
@@ -226,7 +226,7 @@ typedef struct svtme_record_tail {
     uint8_t searched;
     uint8_t do_ref;
     uint8_t tf_early_exit;
-    uint8_t pad[5];
+    uint8_t pad[5]; /* zero, as in svtme_ref_record */
 } svtme_record_tail;
 
 /* Packed host output of svtme_submit_picture_packed_async: per SB, only what the
@@ -242,7 +242,10 @@ typedef struct svtme_record_tail {
  *     uint8  stationary_block_present, rc_me_allow_gm, 0, 0
  *     uint8  total_me_candidate_index[n_pus]
  *     uint8  me_candidate_array[n_pus][max_cand]
- *   zero bytes up to the next multiple of 16. */
+ *   zero bytes up to the next multiple of 16.
+ * The block is a function of the job's outputs alone: the pad bytes of the records and tails
+ * are zero, best_sad is 0xFFFFFFFF on a slot that was not searched, and nothing of the job that
+ * used the ticket's buffers before shows (tests/test_pack.py asserts each against the oracle). */
 typedef struct svtme_pack_layout {
     uint16_t n_pus;       /* PUs with candidates: 85, 21 (no 8x8) or 5 (no 16x16) */
     uint8_t max_cand;     /* pa_me_data->max_cand, 1 .. SVTME_MAX_PA_ME_CAND */

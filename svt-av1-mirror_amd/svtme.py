@@ -753,8 +753,18 @@ def _job_api_protos(lib):
         _proto(lib, "svtme_submit_picture_device", "restype", C.c_int32)
         _proto(lib, "svtme_submit_picture_packed_async", "argtypes", [vp, C.c_uint32, C.POINTER(Job), C.POINTER(PackLayout), vp, C.POINTER(C.c_uint64)])
         _proto(lib, "svtme_submit_picture_packed_async", "restype", C.c_int32)
+        _proto(lib, "svtme_submit_pictures_packed_async", "argtypes", [vp, C.c_uint32, C.c_uint32, C.POINTER(Job),
+                                                                       C.POINTER(PackLayout), C.POINTER(vp),
+                                                                       C.POINTER(C.c_uint64)])
+        _proto(lib, "svtme_submit_pictures_packed_async", "restype", C.c_int32)
         _proto(lib, "svtme_ticket_wait", "argtypes", [vp, C.c_uint64])
         _proto(lib, "svtme_ticket_wait", "restype", C.c_int32)
+        _proto(lib, "svtme_ticket_wait_timed", "argtypes", [vp, C.c_uint64, C.POINTER(C.c_float), C.POINTER(C.c_float)])
+        _proto(lib, "svtme_ticket_wait_timed", "restype", C.c_int32)
+        _proto(lib, "svtme_host_register", "argtypes", [vp, C.c_uint64])
+        _proto(lib, "svtme_host_register", "restype", C.c_int32)
+        _proto(lib, "svtme_host_unregister", "argtypes", [vp])
+        _proto(lib, "svtme_host_unregister", "restype", C.c_int32)
         _proto(lib, "svtme_host_alloc", "argtypes", [C.c_uint64])
         _proto(lib, "svtme_host_alloc", "restype", vp)
         _proto(lib, "svtme_host_free", "argtypes", [vp])
@@ -1021,6 +1031,33 @@ class GpuME:
         if not wait:
             return t.value, ptr, nbytes
         return self.wait_packed(t.value, ptr, nbytes)
+
+    def submit_packed_batch(self, jobs, layouts, lane: int = 0):
+        """svtme_submit_pictures_packed_async: the jobs in one batched launch, job k packed by
+        layouts[k] into its own page-locked buffer under its own ticket; returns
+        [(ticket, pointer, bytes)], each for wait_packed (in any order)."""
+        n = len(jobs)
+        sizes = []
+        for job, L in zip(jobs, layouts):
+            total = sb_total(job.width, job.height)
+            count = job.sb_count if job.sb_count else total - job.sb_begin
+            sizes.append(count * packed_sb_bytes(L, ref_slots(job)))
+        ptrs = [self.lib.svtme_host_alloc(b) for b in sizes]
+        tickets = (C.c_uint64 * n)()
+        st = -1
+        try:
+            if not all(ptrs):
+                raise RuntimeError("svtme_host_alloc failed")
+            st = self.lib.svtme_submit_pictures_packed_async(self.ctx, lane, n, (Job * n)(*jobs),
+                                                             (PackLayout * n)(*layouts), (C.c_void_p * n)(*ptrs),
+                                                             tickets)
+            self._check(st, "svtme_submit_pictures_packed_async")
+        finally:
+            if st != 0:
+                for p in ptrs:
+                    if p:
+                        self.lib.svtme_host_free(p)
+        return [(tickets[k], ptrs[k], sizes[k]) for k in range(n)]
 
     def wait_packed(self, ticket: int, ptr: int, nbytes: int) -> bytes:
         try:

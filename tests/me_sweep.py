@@ -25,6 +25,8 @@ The draws stay inside what the kernels hold ("The ME sweep"):
 No case was taken off the list.
 """
 import ctypes as C
+import json
+import os
 
 U32 = 0xFFFFFFFF
 CUR = 8  # the current picture's time; references are times around it
@@ -316,6 +318,32 @@ def run_cpu(S, case, checker: str = "oracle", frames=None, ctrl=None):
     refs = {(0, i): pyr[t] for i, t in enumerate(case["l0"])}
     refs.update({(1, i): pyr[t] for i, t in enumerate(case["l1"])})
     return S.run_checker(job_of(S, case, ctrl), pyr[CUR], refs, checker, nthreads=8)
+
+
+# ----------------------------------------------------------------------------
+# the committed list and the oracle's outputs of its cases, shared by every test file of a process
+# ----------------------------------------------------------------------------
+_fixture, _oracle = [], {}
+
+
+def fixture() -> dict:
+    """tests/golden/me_sweep.json: the cases with the reference's checksums and coverage."""
+    if not _fixture:
+        with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "me_sweep.json")) as fh:
+            _fixture.append(json.load(fh))
+    return _fixture[0]
+
+
+def oracle_of(S, k):
+    """(controls, records, SB results) of committed case k on the oracle, computed once (read-only)."""
+    if k not in _oracle:
+        case = fixture()["cases"][k]["case"]
+        ctrl = controls_of(S, case)
+        recs, sbr = run_cpu(S, case, "oracle", ctrl=ctrl)
+        for a in (recs, sbr):
+            a.setflags(write=False)
+        _oracle[k] = (ctrl, recs, sbr)
+    return _oracle[k]
 
 
 # ----------------------------------------------------------------------------

@@ -521,8 +521,6 @@ def test_batched_packed_jobs(svtme, gpu):
     """svtme_submit_pictures_packed_async: several jobs (a TF window's
     (central, reference) pairs) in ONE launch, each with its own ticket and
     host output, equal the same jobs submitted one by one."""
-    import ctypes as C
-
     S = svtme
     w, h = 640, 360
     syn = S.Synth(w, h)
@@ -534,21 +532,9 @@ def test_batched_packed_jobs(svtme, gpu):
     L = S.PackLayout()
     L.n_pus, L.max_cand, L.max_refs, L.full_records, L.sb_results = 0, 0, 0, 1, 0
     exp = [gpu.submit_packed(j, L) for j in jobs]
-    n = len(jobs)
-    nbytes = len(exp[0])
-    ptrs = [gpu.lib.svtme_host_alloc(nbytes) for _ in range(n)]
-    arr_jobs = (S.Job * n)(*jobs)
-    arr_l = (S.PackLayout * n)(*([L] * n))
-    arr_p = (C.c_void_p * n)(*ptrs)
-    tickets = (C.c_uint64 * n)()
-    gpu.lib.svtme_submit_pictures_packed_async.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(S.Job),
-                                                           C.POINTER(S.PackLayout), C.POINTER(C.c_void_p),
-                                                           C.POINTER(C.c_uint64)]
-    gpu.lib.svtme_submit_pictures_packed_async.restype = C.c_int32
-    gpu._check(gpu.lib.svtme_submit_pictures_packed_async(gpu.ctx, 1, n, arr_jobs, arr_l, arr_p, tickets),
-               "svtme_submit_pictures_packed_async")
-    for k in reversed(range(n)):  # retired in any order
-        assert gpu.wait_packed(tickets[k], ptrs[k], nbytes) == exp[k], k
+    pend = gpu.submit_packed_batch(jobs, [L] * len(jobs), lane=1)
+    for k in reversed(range(len(jobs))):  # retired in any order
+        assert gpu.wait_packed(*pend[k]) == exp[k], k
     for t in range(4, 13):
         gpu.release(7100 + t)
 

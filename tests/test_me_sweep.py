@@ -21,24 +21,10 @@ for p in (GOLD, HERE):
 
 import me_sweep as M  # noqa: E402
 
-with open(os.path.join(GOLD, "me_sweep.json")) as _fh:
-    FIXTURE = json.load(_fh)
+FIXTURE = M.fixture()
 ENTRIES = FIXTURE["cases"]
 BASE = 20000  # picture numbers of this file's GPU tests: BASE + 100 * case index + time
-
-_oracle = {}
-
-
-def oracle_of(S, k):
-    """The oracle's outputs of case k, computed once and shared (read-only)."""
-    if k not in _oracle:
-        case = ENTRIES[k]["case"]
-        ctrl = M.controls_of(S, case)
-        recs, sbr = M.run_cpu(S, case, "oracle", ctrl=ctrl)
-        for a in (recs, sbr):
-            a.setflags(write=False)
-        _oracle[k] = (ctrl, recs, sbr)
-    return _oracle[k]
+oracle_of = M.oracle_of  # the oracle's outputs of case k, computed once per process and shared
 
 
 def test_committed_list_is_the_generator(svtme):
