@@ -151,7 +151,6 @@ extern "C" svtme_status svtme_ctx_create(int device, svtme_ctx **out) {
     if ((e = svtme_prime_pyramid()) != hipSuccess || (e = svtme_prime_pack()) != hipSuccess ||
         (e = svtme_prime_stages()) != hipSuccess || (e = svtme_prime_dg()) != hipSuccess ||
         (e = svtme_prime_tfsp()) != hipSuccess || (e = svtme_prime_tff()) != hipSuccess ||
-        (e = svtme_prime_tffh()) != hipSuccess || (e = svtme_prime_tffhc()) != hipSuccess ||
         (e = svtme_prime_tfld()) != hipSuccess) {
         (void)hipStreamDestroy(c->stream);
         delete c;

@@ -237,11 +237,31 @@ static inline void svtme_hbd_chroma_geometry(uint32_t W, uint32_t H, uint32_t *w
     *rows   = *h + 2 * *top;
 }
 
-// Arguments of the chroma stage of temporal filtering (svtme_tff.hip: k_tff_pred_uv, k_tff_norm_uv,
-// k_tff_norm_uv_pic), filled by the host. Plane 0 is Cb, 1 is Cr; every picture of a window has the
-// same chroma geometry, so the references are base pointers with one stride.
-struct TffcArgs {
-    DevPlane cen_y;                                // level 0 of the centre picture
+// Arguments of temporal filtering's two stages (svtme_tff.hip), filled by the host
+// (svtme_windows.cpp) and checked by svtme_launch_tf_stage. As in TfldArgs the planes are addressed
+// in bytes at either depth and the launcher's `hbd` chooses the sample type: at 8 bit the luma planes
+// are level 0 and the chroma planes the attached 8-bit ones, at 10 bit the attached 16-bit planes.
+// Strides are in bytes; a DevPlane's width and height are in samples.
+// The luma stage: k_tff_pred, k_tff_norm.
+struct TfLumaArgs {
+    DevPlane cen;                       // the centre picture's plane
+    DevPlane ref[SVTME_MAX_BATCH_JOBS]; // the references'
+    const svtme_tf_subpel_sb *sub;      // [n][sbs]
+    uint8_t *tile;                      // [n][sbs][64 * 64] predictions
+    uint32_t *wgt;                      // [n][sbs][16] weights, 32x32 block * 4 + quarter
+    uint32_t *e32;                      // [n][sbs][4] 32x32 errors
+    uint8_t *plane;                     // dense: the filtered plane, whole SBs, pic_w_b64 * 64 samples a row
+    DevPlane dst;                       // into the result picture: its plane (may be cen)
+    DevPlane dst8;                      //   10 bit: and its level 0, the MSB plane; unused at 8 bit
+    uint32_t decay, dist_th, ss;        // svtme_tf_filter_controls
+    uint32_t n, sbs, pic_w_b64;
+    int32_t W, H; // the 8-aligned picture
+};
+
+// The chroma stage: k_tff_pred_uv, k_tff_norm_uv. Plane 0 is Cb, 1 is Cr; every picture of a
+// window has the same chroma geometry, so the references are base pointers with one stride.
+struct TfChromaArgs {
+    DevPlane cen_y;                                // the centre picture's luma plane
     DevPlane cen[2];                               // its chroma planes
     const uint8_t *ref[2][SVTME_MAX_BATCH_JOBS];   // interior sample (0, 0) of the references' chroma planes
     int32_t ref_stride;
@@ -250,27 +270,8 @@ struct TffcArgs {
     const uint32_t *e32;                           // [n][sbs][4] 32x32 errors (k_tff_pred)
     uint8_t *tile;                                 // [n][sbs][2][32 * 32] chroma predictions
     uint32_t *wgt;                                 // [n][sbs][2][16] chroma weights
-    uint8_t *plane;                                // k_tff_norm_uv: [2] planes of whole SBs, stride pic_w_b64 * 32
-    DevPlane dst[2];                               // k_tff_norm_uv_pic: the result picture's chroma (may be cen)
-    uint32_t decay_cb, decay_cr, dist_th;
-    uint32_t n, sbs, pic_w_b64;
-    int32_t W, H;                                  // the 8-aligned luma size
-};
-
-// Arguments of the 10-bit chroma stage (svtme_tffhc.hip: k_tffh_pred_uv, k_tffh_norm_uv,
-// k_tffh_norm_uv_pic): TffcArgs on the 16-bit planes. Strides are in bytes, tiles and planes in samples.
-struct TffhcArgs {
-    DevPlane cen_y;                                // the centre picture's 16-bit luma plane
-    DevPlane cen[2];                               // its 16-bit chroma planes
-    const uint8_t *ref[2][SVTME_MAX_BATCH_JOBS];   // interior sample (0, 0) of the references' 16-bit chroma planes
-    int32_t ref_stride;                            // bytes
-    const svtme_tf_subpel_sb *sub;                 // [n][sbs]
-    const uint16_t *tile_y;                        // [n][sbs][64 * 64] luma predictions (k_tffh_pred)
-    const uint32_t *e32;                           // [n][sbs][4] 32x32 errors (k_tffh_pred)
-    uint16_t *tile;                                // [n][sbs][2][32 * 32] chroma predictions
-    uint32_t *wgt;                                 // [n][sbs][2][16] chroma weights
-    uint16_t *plane;                               // k_tffh_norm_uv: [2] planes of whole SBs, pic_w_b64 * 32 samples a row
-    DevPlane dst[2];                               // k_tffh_norm_uv_pic: the result picture's 16-bit chroma (may be cen)
+    uint8_t *plane;                                // dense: [2] planes of whole SBs, pic_w_b64 * 32 samples a row
+    DevPlane dst[2];                               // into the result picture: its chroma planes (may be cen)
     uint32_t decay_cb, decay_cr, dist_th;
     uint32_t n, sbs, pic_w_b64;
     int32_t W, H;                                  // the 8-aligned luma size
@@ -293,17 +294,12 @@ struct TfldArgs {
     int32_t W, H; // the 8-aligned luma size
 };
 
-// Bytes per unit (one reference's SB) of the temporal filter's scratch sections, as svtme_tff.hip
-// indexes them; the host lays the sections out by these (TfScratch, svtme_windows.cpp).
-#define SVTME_TFF_TILE_BYTES 4096   // luma prediction: k_tff_pred / k_tff_norm, `A.tile + unit * 4096`
+// Bytes per unit (one reference's SB) of the temporal filter's scratch sections at 8 bit, as
+// svtme_tff.hip indexes them; the host lays the sections out by these (TfScratch, svtme_windows.cpp).
+// At 10 bit the sections of samples (tiles, dense planes) hold two bytes a sample: these times two.
+#define SVTME_TFF_TILE_BYTES 4096   // luma prediction: 64 x 64 samples (the dense luma plane holds as much per SB)
 #define SVTME_TFF_WGT_BYTES 64      // luma weights: `A.wgt[unit * 16 + ...]`, 16 dwords
 #define SVTME_TFF_E32_BYTES 16      // 32x32 errors: `A.e32[unit * 4 + ...]`, 4 dwords
-#define SVTME_TFFC_TILE_BYTES 2048  // Cb and Cr predictions: k_tff_pred_uv / k_tff_norm_uv, `A.tile + unit * 2048`
+#define SVTME_TFFC_TILE_BYTES 2048  // Cb and Cr predictions: 2 x 32 x 32 samples
 #define SVTME_TFFC_WGT_BYTES 128    // chroma weights: `A.wgt[unit * 32 + ...]`, 32 dwords
-#define SVTME_TFFC_PLANE_SB_BYTES 1024 // one SB of one dense chroma plane: k_tff_norm_uv, `pl * A.sbs * 1024`
-// (the dense luma plane of k_tff_norm holds SVTME_TFF_TILE_BYTES per SB: whole 64 x 64 SBs)
-#define SVTME_TFFH_TILE_BYTES 8192  // 16-bit luma prediction: k_tffh_pred / k_tffh_norm, `A.tile + unit * 4096` samples
-// (svtme_tffh.hip shares the weight and error sections; its dense plane holds SVTME_TFFH_TILE_BYTES per SB)
-#define SVTME_TFFHC_TILE_BYTES 4096 // 16-bit Cb and Cr predictions: k_tffh_pred_uv / k_tffh_norm_uv, `A.tile + unit * 2048` samples
-#define SVTME_TFFHC_PLANE_SB_BYTES 2048 // one SB of one dense 16-bit chroma plane: k_tffh_norm_uv, `pl * A.sbs * 1024` samples
-// (svtme_tffhc.hip's weights hold SVTME_TFFC_WGT_BYTES per unit, as the 8-bit chroma stage's)
+#define SVTME_TFFC_PLANE_SB_BYTES 1024 // one SB of one dense chroma plane: 32 x 32 samples

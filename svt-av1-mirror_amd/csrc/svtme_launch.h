@@ -127,6 +127,9 @@ hipError_t svtme_launch_host_rows(const uint8_t *src, uint32_t src_stride, int w
                                   uint32_t dst_stride, hipStream_t s);
 hipError_t svtme_launch_build_full(const void *src, uint32_t src_stride, int w, int h, int ten_bit, DevPlane dst,
                                    int left, int top, int rows, hipStream_t s);
+// an attached 16-bit plane (svtme_hbd_geometry, svtme_hbd_chroma_geometry); src_stride in samples
+hipError_t svtme_launch_build_full16(const uint16_t *src, uint32_t src_stride, int w, int h, DevPlane dst, int left,
+                                     int top, int rows, hipStream_t s);
 hipError_t svtme_launch_build_down(DevPlane prev, DevPlane dst, int left, int top, int rows, hipStream_t s);
 hipError_t svtme_launch_copy_words(const void *src, void *dst, uint32_t nwords, hipStream_t s);
 hipError_t svtme_prime_pack(void);
@@ -139,37 +142,10 @@ hipError_t svtme_prime_tfsp(void);
 hipError_t svtme_launch_tfsp(const DevPlane *cen, const DevPlane *ref, uint32_t n, uint32_t width, uint32_t height,
                              const svtme_tf_subpel_controls *ctl, const svtme_ref_record *d_rec,
                              svtme_tf_subpel_sb *d_out, hipStream_t s);
+// svtme_tff.hip: temporal filtering's luma stage and, with U, its chroma stage; hbd: the 16-bit planes;
+// pic: the normalisation into the result picture (Y->dst, U->dst), else into the dense planes
 hipError_t svtme_prime_tff(void);
-hipError_t svtme_launch_tff(const DevPlane *cen, const DevPlane *ref, uint32_t n, uint32_t width, uint32_t height,
-                            const svtme_tf_filter_controls *ctl, const svtme_tf_subpel_sb *d_sub, uint8_t *d_tile,
-                            uint32_t *d_wgt, uint32_t *d_e32, uint8_t *d_plane, hipStream_t s);
-hipError_t svtme_launch_tff_pic(const DevPlane *cen, const DevPlane *ref, uint32_t n, uint32_t width, uint32_t height,
-                                const svtme_tf_filter_controls *ctl, const svtme_tf_subpel_sb *d_sub, uint8_t *d_tile,
-                                uint32_t *d_wgt, uint32_t *d_e32, const DevPlane *dst, hipStream_t s);
-hipError_t svtme_launch_tffc(const TffcArgs *A, hipStream_t s);
-hipError_t svtme_launch_tff_pic_yuv(const DevPlane *cen, const DevPlane *ref, uint32_t n, uint32_t width,
-                                    uint32_t height, const svtme_tf_filter_controls *ctl,
-                                    const svtme_tf_subpel_sb *d_sub, uint8_t *d_tile, uint32_t *d_wgt, uint32_t *d_e32,
-                                    const DevPlane *dst, const TffcArgs *U, hipStream_t s);
-// svtme_tffh.hip: the 10-bit filter; its planes are 16-bit (svtme_hbd_geometry), src_stride in samples
-hipError_t svtme_prime_tffh(void);
-hipError_t svtme_launch_build_full16(const uint16_t *src, uint32_t src_stride, int w, int h, DevPlane dst, int left,
-                                     int top, int rows, hipStream_t s);
-hipError_t svtme_launch_tffh(const DevPlane *cen, const DevPlane *ref, uint32_t n, uint32_t width, uint32_t height,
-                             const svtme_tf_filter_controls *ctl, const svtme_tf_subpel_sb *d_sub, uint16_t *d_tile,
-                             uint32_t *d_wgt, uint32_t *d_e32, uint16_t *d_plane, hipStream_t s);
-hipError_t svtme_launch_tffh_pic(const DevPlane *cen, const DevPlane *ref, uint32_t n, uint32_t width, uint32_t height,
-                                 const svtme_tf_filter_controls *ctl, const svtme_tf_subpel_sb *d_sub, uint16_t *d_tile,
-                                 uint32_t *d_wgt, uint32_t *d_e32, const DevPlane *dst, const DevPlane *dst8,
-                                 hipStream_t s);
-// svtme_tffhc.hip: the 10-bit chroma stage. svtme_launch_tffhc follows svtme_launch_tffh on `s`;
-// svtme_launch_tffh_pic_yuv is svtme_launch_tffh_pic with the chroma stage between and after its two steps
-hipError_t svtme_prime_tffhc(void);
-hipError_t svtme_launch_tffhc(const TffhcArgs *A, hipStream_t s);
-hipError_t svtme_launch_tffh_pic_yuv(const DevPlane *cen, const DevPlane *ref, uint32_t n, uint32_t width,
-                                     uint32_t height, const svtme_tf_filter_controls *ctl,
-                                     const svtme_tf_subpel_sb *d_sub, uint16_t *d_tile, uint32_t *d_wgt, uint32_t *d_e32,
-                                     const DevPlane *dst, const DevPlane *dst8, const TffhcArgs *U, hipStream_t s);
+hipError_t svtme_launch_tf_stage(const TfLumaArgs *Y, const TfChromaArgs *U, int hbd, int pic, hipStream_t s);
 // svtme_tfld.hip: the low-delay filter, one fused kernel; hbd: 16-bit planes, chroma: Cb and Cr too
 hipError_t svtme_prime_tfld(void);
 hipError_t svtme_launch_tfld(const TfldArgs *A, int hbd, int chroma, hipStream_t s);

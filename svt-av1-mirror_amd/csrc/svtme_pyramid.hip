@@ -2,6 +2,7 @@
 //
 //   k_build_full<TEN_BIT> : full-resolution plane, pad-to-8 + edge replication
 //                           (10-bit input reduced to its MSB plane, enc_handle.c:4964-4972)
+//   k_build_full16        : the same for an attached 16-bit plane (luma or chroma), samples kept whole
 //   k_build_down          : 1/4 and 1/16 planes, (a+b+c+d+2)>>2 of the level above
 //                           (svt_aom_downsample_2d_c, pic_analysis_process.c:130-158;
 //                            svt_aom_downsample_filtering_input_picture :1945-2002;
@@ -53,6 +54,27 @@ __global__ void __launch_bounds__(256) k_build_full(const void *src, uint32_t sr
     }
     uint32_t *row = (uint32_t *)(dst.base - (size_t)top * dst.stride - left);
     row[idx]      = v;
+}
+
+// The padded 16-bit plane from w x h true samples, two samples a thread: the replication to the
+// aligned size and the margins are one clamp of the source coordinate (k_build_full's scheme). With
+// pad_only the source is the plane's own interior: the dwords wholly inside it are left alone, the
+// others are written from samples no thread changes. The geometry comes as parameters: the chroma
+// margins serve it as the luma's do.
+__global__ void __launch_bounds__(256) k_build_full16(const uint16_t *src, uint32_t src_stride, int w, int h,
+                                                      DevPlane dst, int left, int top, int rows, int pad_only) {
+    const int dw_per_row = dst.stride >> 2;
+    const int idx        = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= dw_per_row * rows)
+        return;
+    const int ry = idx / dw_per_row, x0 = (idx - ry * dw_per_row) * 2 - left;
+    if (pad_only && x0 >= 0 && x0 + 1 < w && ry >= top && ry - top < h)
+        return;
+    const int y  = min(max(ry - top, 0), h - 1);
+    const int xa = min(max(x0, 0), w - 1), xb = min(max(x0 + 1, 0), w - 1);
+    const uint16_t *sr = src + (size_t)y * src_stride;
+    uint32_t *row = (uint32_t *)(dst.base - (ptrdiff_t)top * dst.stride - (ptrdiff_t)left * 2);
+    row[idx]      = (uint32_t)sr[xa] | ((uint32_t)sr[xb] << 16);
 }
 
 // levels 1, 2: 2x2 mean (sum + 2) >> 2 of the previous level's interior, edge replicate
@@ -137,6 +159,16 @@ extern "C" hipError_t svtme_launch_build_full(const void *src, uint32_t src_stri
     else
         hipLaunchKernelGGL(k_build_full<false>, dim3((n + 255) / 256), dim3(256), 0, s, src, src_stride, w, h, dst,
                            left, top, rows, pad_only);
+    return hipGetLastError();
+}
+
+// src_stride in samples; in place (the interior already in the plane): margins only
+extern "C" hipError_t svtme_launch_build_full16(const uint16_t *src, uint32_t src_stride, int w, int h, DevPlane dst,
+                                                int left, int top, int rows, hipStream_t s) {
+    const int n        = (dst.stride >> 2) * rows;
+    const int pad_only = (const uint8_t *)src == dst.base && src_stride * 2 == (uint32_t)dst.stride;
+    hipLaunchKernelGGL(k_build_full16, dim3((n + 255) / 256), dim3(256), 0, s, src, src_stride, w, h, dst, left, top,
+                       rows, pad_only);
     return hipGetLastError();
 }
 

@@ -42,94 +42,9 @@
 #include <stdint.h>
 
 #include "svtme_launch.h"
-#include "svtme_me_common.h"
+#include "svtme_tf_common.h"
 
 using namespace svtme;
-
-// floor(exp(-i / 16) * 2^16), computed as svtme_tff.hip computes it
-struct TfldExpTab {
-    int32_t v[113];
-};
-constexpr TfldExpTab tfld_make_exp() {
-    TfldExpTab t{};
-    double r = 1.0, term = 1.0;
-    for (int k = 1; k < 24; k++) {
-        term *= -0.0625 / k;
-        r += term;
-    }
-    double p = 1.0;
-    for (int i = 0; i < 113; i++) {
-        t.v[i] = (int32_t)(p * 65536.0);
-        p *= r;
-    }
-    return t;
-}
-__constant__ TfldExpTab c_tfld_exp = tfld_make_exp();
-
-// N samples of type T at p (aligned to N * sizeof(T) bytes: 4, 8, 16 or 32), one per element of v
-template <typename T, int N>
-__device__ __forceinline__ void tfld_load(const uint8_t *p, uint32_t v[N]) {
-    constexpr int DW = N * (int)sizeof(T) / 4;
-    uint32_t w[DW];
-    if constexpr (DW == 1)
-        w[0] = *(const uint32_t *)p;
-    else if constexpr (DW == 2) {
-        const uint2 a = *(const uint2 *)p;
-        w[0] = a.x, w[1] = a.y;
-    } else {
-#pragma unroll
-        for (int i = 0; i < DW / 4; i++) {
-            const uint4 a = ((const uint4 *)p)[i];
-            w[4 * i] = a.x, w[4 * i + 1] = a.y, w[4 * i + 2] = a.z, w[4 * i + 3] = a.w;
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < N; k++)
-        v[k] = sizeof(T) == 1 ? (w[k >> 2] >> (8 * (k & 3))) & 0xFFu : (w[k >> 1] >> (16 * (k & 1))) & 0xFFFFu;
-}
-
-// the first `count` (N or N / 2) of N samples of type T to p, packed; shift: >> 2 into bytes (level 0 of a 10-bit result)
-template <typename T, int N>
-__device__ __forceinline__ void tfld_store(uint8_t *p, const uint32_t v[N], bool half) {
-    constexpr int DW = N * (int)sizeof(T) / 4;
-    uint32_t w[DW];
-#pragma unroll
-    for (int i = 0; i < DW; i++) w[i] = 0;
-#pragma unroll
-    for (int k = 0; k < N; k++)
-        if constexpr (sizeof(T) == 1)
-            w[k >> 2] |= (v[k] & 0xFFu) << (8 * (k & 3));
-        else
-            w[k >> 1] |= (v[k] & 0xFFFFu) << (16 * (k & 1));
-    if constexpr (DW == 1)
-        *(uint32_t *)p = w[0];
-    else if constexpr (DW == 2)
-        *(uint2 *)p = make_uint2(w[0], w[1]);
-    else if constexpr (DW == 4) {
-        if (half)
-            *(uint2 *)p = make_uint2(w[0], w[1]);
-        else
-            *(uint4 *)p = make_uint4(w[0], w[1], w[2], w[3]);
-    } else {
-        ((uint4 *)p)[0] = make_uint4(w[0], w[1], w[2], w[3]);
-        if (!half)
-            ((uint4 *)p)[1] = make_uint4(w[4], w[5], w[6], w[7]);
-    }
-}
-
-// (accum + (count >> 1)) / count for N accumulators: count <= 9000 and accum < 2^25, so the high
-// product by 2^32 / count rounded up is the quotient or one more (svtme_tffh.hip's tffh_norm16)
-template <int N>
-__device__ __forceinline__ void tfld_norm(uint32_t acc[N], uint32_t cnt) {
-    const uint32_t m = 0xFFFFFFFFu / cnt + 1u;
-#pragma unroll
-    for (int k = 0; k < N; k++) {
-        const uint32_t v = acc[k] + (cnt >> 1);
-        uint32_t q       = __umulhi(v, m);
-        q -= q * cnt > v;
-        acc[k] = q;
-    }
-}
 
 template <typename T, bool CHROMA>
 __global__ void __launch_bounds__(256) k_tfld(const TfldArgs A) {
@@ -148,13 +63,13 @@ __global__ void __launch_bounds__(256) k_tfld(const TfldArgs A) {
 
     uint32_t cen[16], acc[16], cnt[3] = {1000u, 1000u, 1000u}; // svt_aom_apply_filtering_central[_highbd]_c
     uint32_t cacc[2][4];
-    tfld_load<T, 16>(A.cen_y + yo, cen);
+    tf_load<T, 16>(A.cen_y + yo, cen);
 #pragma unroll
     for (int k = 0; k < 16; k++) acc[k] = 1000u * cen[k];
     if constexpr (CHROMA) {
 #pragma unroll
         for (int p = 0; p < 2; p++) {
-            tfld_load<T, 4>(A.cen_c[p] + co, cacc[p]);
+            tf_load<T, 4>(A.cen_c[p] + co, cacc[p]);
 #pragma unroll
             for (int k = 0; k < 4; k++) cacc[p][k] *= 1000u;
         }
@@ -162,10 +77,10 @@ __global__ void __launch_bounds__(256) k_tfld(const TfldArgs A) {
 
     for (uint32_t r = 0; r < A.n; r++) {
         uint32_t pre[16], cpre[2][4];
-        tfld_load<T, 16>(A.ref_y[r] + yo, pre);
+        tf_load<T, 16>(A.ref_y[r] + yo, pre);
         if constexpr (CHROMA) {
-            tfld_load<T, 4>(A.ref_c[0][r] + co, cpre[0]);
-            tfld_load<T, 4>(A.ref_c[1][r] + co, cpre[1]);
+            tf_load<T, 4>(A.ref_c[0][r] + co, cpre[0]);
+            tf_load<T, 4>(A.ref_c[1][r] + co, cpre[1]);
         }
         int sum      = 0;
         uint32_t sse = 0;
@@ -177,17 +92,8 @@ __global__ void __launch_bounds__(256) k_tfld(const TfldArgs A) {
         }
         const int sk        = (int)wave_sum_u32(kept ? (uint32_t)sum : 0u);
         const uint32_t ssek = wave_sum_u32(kept ? sse : 0u);
-        uint32_t var, e;
-        if constexpr (BPP == 1) {
-            var = (ssek - (uint32_t)(((int64_t)sk * sk) >> (10 - ss))) << ss; // / (32 * (32 >> shift))
-            e   = var >> 2;                                                  // (:831)
-        } else {
-            const uint32_t s4 = (ssek + 8u) >> 4;
-            const int s2      = (sk + 2) >> 2;
-            const int64_t v   = (int64_t)s4 - (((int64_t)s2 * s2) >> (10 - ss));
-            var               = (uint32_t)(v >= 0 ? v : 0) << ss;
-            e                 = var >> 6; // (:933)
-        }
+        const uint32_t var = tf_var32<T>(sk, ssek, ss);
+        const uint32_t e   = var >> (BPP == 1 ? 2 : 6); // (:831, :933)
         if (A.var32 && lane == 0)
             A.var32[((size_t)r * A.sbs + b64) * 4 + wid] = var;
         uint32_t w[3];
@@ -196,7 +102,7 @@ __global__ void __launch_bounds__(256) k_tfld(const TfldArgs A) {
             const uint32_t dd = (A.decay[p] >> 10) ? (A.decay[p] >> 10) : 1u;
             uint32_t sd       = (e << 2) / dd;
             sd                = sd < 112u ? sd : 112u;
-            w[p]              = (uint32_t)(c_tfld_exp.v[sd] * 1000) >> 17;
+            w[p]              = (uint32_t)(c_tf_exp.v[sd] * 1000) >> 17;
             cnt[p] += w[p];
         }
 #pragma unroll
@@ -210,14 +116,14 @@ __global__ void __launch_bounds__(256) k_tfld(const TfldArgs A) {
     }
 
     if (x < A.W && y < A.H) {
-        tfld_norm<16>(acc, cnt[0]);
+        tf_norm<16>(acc, cnt[0]);
         const bool half = x + 16 > A.W;
-        tfld_store<T, 16>(A.dst_y.base + (ptrdiff_t)y * A.dst_y.stride + (ptrdiff_t)x * BPP, acc, half);
+        tf_store<T, 16>(A.dst_y.base + (ptrdiff_t)y * A.dst_y.stride + (ptrdiff_t)x * BPP, acc, half);
         if constexpr (BPP == 2) {
             if (A.dst8.base) { // the result picture's level 0: the MSB plane
 #pragma unroll
                 for (int k = 0; k < 16; k++) acc[k] >>= 2;
-                tfld_store<uint8_t, 16>(A.dst8.base + (ptrdiff_t)y * A.dst8.stride + x, acc, half);
+                tf_store<uint8_t, 16>(A.dst8.base + (ptrdiff_t)y * A.dst8.stride + x, acc, half);
             }
         }
     }
@@ -226,8 +132,8 @@ __global__ void __launch_bounds__(256) k_tfld(const TfldArgs A) {
 #pragma unroll
             for (int p = 0; p < 2; p++)
                 if (A.dst_c[p].base) {
-                    tfld_norm<4>(cacc[p], cnt[1 + p]);
-                    tfld_store<T, 4>(A.dst_c[p].base + (ptrdiff_t)cy * A.dst_c[p].stride + (ptrdiff_t)cx * BPP, cacc[p],
+                    tf_norm<4>(cacc[p], cnt[1 + p]);
+                    tf_store<T, 4>(A.dst_c[p].base + (ptrdiff_t)cy * A.dst_c[p].stride + (ptrdiff_t)cx * BPP, cacc[p],
                                      false);
                 }
         }

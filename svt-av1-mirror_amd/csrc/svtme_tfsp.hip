@@ -69,7 +69,7 @@
 #include <stdint.h>
 
 #include "svtme_launch.h"
-#include "svtme_me_common.h"
+#include "svtme_tf_common.h"
 
 using namespace svtme;
 
@@ -116,17 +116,6 @@ __device__ __forceinline__ int tf_hsum(const uint8_t *p, const int t[8], bool bi
 }
 
 __device__ __forceinline__ int tf_clip8(int v) { return v < 0 ? 0 : v > 255 ? 255 : v; }
-
-// origin of block k (Z order) of level lv (0: 64x64 .. 3: 8x8) inside the SB
-__device__ __forceinline__ void tf_block_xy(int lv, int k, int *x, int *y) {
-    int bx = 0, by = 0;
-    for (int j = 0; j < lv; j++) {
-        const int pair = (k >> (2 * (lv - 1 - j))) & 3;
-        bx += (pair & 1) * (32 >> j);
-        by += (pair >> 1) * (32 >> j);
-    }
-    *x = bx, *y = by;
-}
 
 // One unit on one wavefront: the variance (<< shift) of the b x b block at (px, py) of the centre
 // picture against the reference block the 1/8-pel MV points to. `on` is wave-uniform; every
@@ -313,7 +302,7 @@ __global__ void __launch_bounds__(256) k_tfsp(const TfspArgs A) {
                     on = s_act[k] && !(st && md >= 2 && xd && yd);
                 }
                 int bx, by;
-                tf_block_xy(lv, k, &bx, &by);
+                tf_unit_origin(lv, k, 32, &bx, &by);
                 const uint32_t d = tf_eval(A, R, s_win[wid], s_im[wid], (const uint8_t *)s_cen, lane, on, b, sb_x + bx,
                                            sb_y + by, bx, by, (int16_t)(s_cx[k] + xd), (int16_t)(s_cy[k] + yd), bil);
                 if (on && lane == 0)

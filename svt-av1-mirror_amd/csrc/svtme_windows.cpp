@@ -1,9 +1,8 @@
 // svtme_windows.cpp — the calls over a window of resident pictures, all on lane 0: the dynamic-GOP
-// detector (svtme_dg.hip) and temporal filtering's stages (svtme_tfsp.hip, svtme_tff.hip, svtme_tffh.hip,
-// svtme_tffhc.hip), alone
-// and as one window resident to resident, and the low-delay filter (svtme_tfld.hip). Each holds the context lock from its first launch to
-// its last copy, as svtme_submit_picture does: the device outputs are the context's, and a
-// release / invalidate of a picture from another thread waits for the lock.
+// detector (svtme_dg.hip) and temporal filtering's stages (svtme_tfsp.hip, svtme_tff.hip), alone and as
+// one window resident to resident, and the low-delay filter (svtme_tfld.hip). Each holds the context
+// lock from its first launch to its last copy, as svtme_submit_picture does: the device outputs are the
+// context's, and a release / invalidate of a picture from another thread waits for the lock.
 #include <cstring>
 
 #include "svtme_ctx.h"
@@ -139,15 +138,15 @@ static svtme_status tf_scratch(svtme_ctx *c, uint32_t n, uint32_t sbs, bool dens
     const size_t units = (size_t)n * sbs;
     S->sub_bytes    = sizeof(svtme_tf_subpel_sb) * units;
     S->e32_bytes    = SVTME_TFF_E32_BYTES * units;
-    S->cplane_bytes = (size_t)(hbd ? SVTME_TFFHC_PLANE_SB_BYTES : SVTME_TFFC_PLANE_SB_BYTES) * sbs;
+    const size_t bpp = hbd ? 2 : 1;
+    S->cplane_bytes = SVTME_TFFC_PLANE_SB_BYTES * bpp * sbs;
     size_t end = 0;
     auto take  = [&end](bool present, size_t bytes) { // the section's offset; absent sections are empty
         const size_t at = end;
         end += present ? bytes : 0;
         return at;
     };
-    const size_t tile_bytes = hbd ? SVTME_TFFH_TILE_BYTES : SVTME_TFF_TILE_BYTES;
-    const size_t ctile_bytes = hbd ? SVTME_TFFHC_TILE_BYTES : SVTME_TFFC_TILE_BYTES;
+    const size_t tile_bytes = SVTME_TFF_TILE_BYTES * bpp, ctile_bytes = SVTME_TFFC_TILE_BYTES * bpp;
     const size_t o_sub = take(true, S->sub_bytes), o_tile = take(true, tile_bytes * units),
                  o_wgt = take(true, SVTME_TFF_WGT_BYTES * units), o_e32 = take(true, S->e32_bytes),
                  o_plane = take(dense, tile_bytes * sbs),
@@ -187,54 +186,54 @@ static svtme_status chroma_strides_ok(const char *fn, const TfChroma *uv, uint32
     return SVTME_OK;
 }
 
-// the chroma stage's arguments over the scratch of a call with chroma
-static void tffc_fill(TffcArgs &A, PicBuf *const *pb, uint32_t n, uint32_t W, uint32_t H,
-                      const svtme_tf_filter_controls *ctl, const TfChroma *uv, const TfScratch &S) {
-    A.cen_y = pb[0]->pyr.lv[0];
-    for (int p = 0; p < 2; p++) {
-        A.cen[p] = pb[0]->chroma[p];
-        for (uint32_t k = 0; k < SVTME_MAX_BATCH_JOBS; k++) A.ref[p][k] = pb[k < n ? k + 1 : 1]->chroma[p].base;
-    }
-    A.ref_stride = pb[1]->chroma[0].stride;
-    A.sub        = S.sub;
-    A.tile_y     = S.tile;
-    A.e32        = S.e32;
-    A.tile       = S.ctile;
-    A.wgt        = S.cwgt;
-    A.plane      = S.cplane;
-    A.decay_cb   = uv->decay[0];
-    A.decay_cr   = uv->decay[1];
-    A.dist_th    = ctl->tf_mv_dist_th;
-    A.n          = n;
-    A.pic_w_b64  = (W + 63) / 64;
-    A.sbs        = svtme_sb_total(W, H);
-    A.W          = (int32_t)W;
-    A.H          = (int32_t)H;
-}
+// the planes the filters read and write of a picture: level 0 and the attached 8-bit chroma, or (hbd) the
+// attached 16-bit planes
+static const DevPlane &tf_luma(const PicBuf *p, bool hbd) { return hbd ? p->hbd : p->pyr.lv[0]; }
+static const DevPlane &tf_chroma(const PicBuf *p, int pl, bool hbd) { return hbd ? p->hchroma[pl] : p->chroma[pl]; }
 
-// the 10-bit chroma stage's arguments likewise (the luma tiles and planes are the 16-bit ones)
-static void tffhc_fill(TffhcArgs &A, PicBuf *const *pb, uint32_t n, uint32_t W, uint32_t H,
-                       const svtme_tf_filter_controls *ctl, const TfChroma *uv, const TfScratch &S) {
-    A.cen_y = pb[0]->hbd;
+// The two stages' arguments (svtme_launch_tf_stage) over the scratch of a call: the centre pb[0] and the n
+// references behind it. U is filled where the call has chroma (uv). The result picture's planes (Y.dst,
+// Y.dst8, U.dst) are the window call's to set; a dense call leaves them zero and the kernels it launches
+// do not read them.
+static void tf_stage_fill(TfLumaArgs &Y, TfChromaArgs &U, PicBuf *const *pb, uint32_t n, uint32_t W, uint32_t H,
+                          const svtme_tf_filter_controls *ctl, const TfChroma *uv, bool hbd, const TfScratch &S) {
+    Y.cen = tf_luma(pb[0], hbd);
+    for (uint32_t k = 0; k < SVTME_MAX_BATCH_JOBS; k++) Y.ref[k] = tf_luma(pb[k < n ? k + 1 : 1], hbd);
+    Y.sub       = S.sub;
+    Y.tile      = S.tile;
+    Y.wgt       = S.wgt;
+    Y.e32       = S.e32;
+    Y.plane     = S.plane;
+    Y.decay     = ctl->tf_decay_factor_fp16;
+    Y.dist_th   = ctl->tf_mv_dist_th;
+    Y.ss        = ctl->sub_sampling_shift;
+    Y.n         = n;
+    Y.pic_w_b64 = (W + 63) / 64;
+    Y.sbs       = svtme_sb_total(W, H);
+    Y.W         = (int32_t)W;
+    Y.H         = (int32_t)H;
+    if (!uv)
+        return;
+    U.cen_y = Y.cen;
     for (int p = 0; p < 2; p++) {
-        A.cen[p] = pb[0]->hchroma[p];
-        for (uint32_t k = 0; k < SVTME_MAX_BATCH_JOBS; k++) A.ref[p][k] = pb[k < n ? k + 1 : 1]->hchroma[p].base;
+        U.cen[p] = tf_chroma(pb[0], p, hbd);
+        for (uint32_t k = 0; k < SVTME_MAX_BATCH_JOBS; k++) U.ref[p][k] = tf_chroma(pb[k < n ? k + 1 : 1], p, hbd).base;
     }
-    A.ref_stride = pb[1]->hchroma[0].stride;
-    A.sub        = S.sub;
-    A.tile_y     = (const uint16_t *)S.tile;
-    A.e32        = S.e32;
-    A.tile       = (uint16_t *)S.ctile;
-    A.wgt        = S.cwgt;
-    A.plane      = (uint16_t *)S.cplane;
-    A.decay_cb   = uv->decay[0];
-    A.decay_cr   = uv->decay[1];
-    A.dist_th    = ctl->tf_mv_dist_th;
-    A.n          = n;
-    A.pic_w_b64  = (W + 63) / 64;
-    A.sbs        = svtme_sb_total(W, H);
-    A.W          = (int32_t)W;
-    A.H          = (int32_t)H;
+    U.ref_stride = tf_chroma(pb[1], 0, hbd).stride;
+    U.sub        = S.sub;
+    U.tile_y     = S.tile;
+    U.e32        = S.e32;
+    U.tile       = S.ctile;
+    U.wgt        = S.cwgt;
+    U.plane      = S.cplane;
+    U.decay_cb   = uv->decay[0];
+    U.decay_cr   = uv->decay[1];
+    U.dist_th    = ctl->tf_mv_dist_th;
+    U.n          = n;
+    U.pic_w_b64  = Y.pic_w_b64;
+    U.sbs        = Y.sbs;
+    U.W          = Y.W;
+    U.H          = Y.H;
 }
 
 // ---- Temporal filtering's sub-pel refinement (svtme_tfsp.hip) ----
@@ -310,36 +309,26 @@ static svtme_status tf_filter_impl(const char *fn, const TfChroma *uv, const TfH
     memcpy(pn + 1, ref_picture_numbers, n * sizeof(uint64_t));
     std::lock_guard<std::mutex> lk(c->mu);
     PicBuf *pb[SVTME_MAX_BATCH_JOBS + 1];
-    if ((st = resident_pics(c, fn, pn, n + 1, W, H, uv && !hb, pb, hb != nullptr, uv && hb)))
+    const bool hbd = hb != nullptr;
+    if ((st = resident_pics(c, fn, pn, n + 1, W, H, uv && !hbd, pb, hbd, uv && hbd)))
         return st;
     HIP_TRY(hipSetDevice(c->device));
     TfScratch S;
     DevPlane ref[SVTME_MAX_BATCH_JOBS];
-    if ((st = tf_scratch(c, n, sbs, true, uv != nullptr, &S, hb != nullptr)) || (st = join_window(c, pb, n, ref)))
+    if ((st = tf_scratch(c, n, sbs, true, uv != nullptr, &S, hbd)) || (st = join_window(c, pb, n, ref)))
         return st;
     Lane &L              = c->lanes[0];
     const size_t pstride = (size_t)((W + 63) / 64) * 64; // of the dense luma plane; the chroma planes' is half
     HIP_TRY(hipMemcpyAsync(S.sub, subpel, S.sub_bytes, hipMemcpyHostToDevice, L.s));
-    if (hb) {
-        for (uint32_t k = 0; k < n; k++) ref[k] = pb[k + 1]->hbd;
-        HIP_TRY(svtme_launch_tffh(&pb[0]->hbd, ref, n, W, H, ctl, S.sub, (uint16_t *)S.tile, S.wgt, S.e32,
-                                  (uint16_t *)S.plane, L.s));
-    } else
-        HIP_TRY(svtme_launch_tff(&pb[0]->pyr.lv[0], ref, n, W, H, ctl, S.sub, S.tile, S.wgt, S.e32, S.plane, L.s));
-    if (uv && hb) {
-        TffhcArgs U{};
-        tffhc_fill(U, pb, n, W, H, ctl, uv, S);
-        HIP_TRY(svtme_launch_tffhc(&U, L.s));
-    } else if (uv) {
-        TffcArgs U{};
-        tffc_fill(U, pb, n, W, H, ctl, uv, S);
-        HIP_TRY(svtme_launch_tffc(&U, L.s));
-    }
+    TfLumaArgs Y{};
+    TfChromaArgs U{};
+    tf_stage_fill(Y, U, pb, n, W, H, ctl, uv, hbd, S);
+    HIP_TRY(svtme_launch_tf_stage(&Y, uv ? &U : nullptr, hbd, 0, L.s));
     hipEvent_t done;
     if ((st = submission_done(L, &done)))
         return st;
     mark_read(pb, n + 1, 0, done);
-    const size_t bpp = hb ? 2 : 1;
+    const size_t bpp = hbd ? 2 : 1;
     HIP_TRY(hipMemcpy2DAsync(out, out_stride * bpp, S.plane, pstride * bpp, width * bpp, height, hipMemcpyDeviceToHost,
                              L.s));
     if (err32_out)
@@ -390,8 +379,8 @@ extern "C" svtme_status svtme_tf_filter_10bit(svtme_ctx *c, uint64_t centre_pict
 // stream through the two stages' scratch.
 // ----------------------------------------------------------------------------
 // svtme_tf_window (uv and hb NULL), svtme_tf_window_yuv (uv), svtme_tf_window_10bit (hb: the TF-ME
-// batch and k_tfsp on the MSB planes as ever, then svtme_tffh.hip on the 16-bit planes) and
-// svtme_tf_window_yuv_10bit (both: svtme_tffhc.hip's chroma stage beside it)
+// batch and k_tfsp on the MSB planes as ever, then svtme_tff.hip on the 16-bit planes) and
+// svtme_tf_window_yuv_10bit (both)
 static svtme_status tf_window_impl(const char *fn, const TfChroma *uv, const TfHbd *hb, svtme_ctx *c,
                                    const svtme_job *jobs, uint32_t n,
                                    uint32_t src_width, uint32_t src_height, const svtme_tf_subpel_controls *sp_ctl,
@@ -446,14 +435,14 @@ static svtme_status tf_window_impl(const char *fn, const TfChroma *uv, const TfH
     // the batch and the result picture's allocation: std::map keeps its other nodes where they
     // are, and the result picture, where it is the centre, has the centre's size and stays too.
     PicBuf *pb[SVTME_MAX_BATCH_JOBS + 1];
-    const bool uv8 = uv && !hb, uv16 = uv && hb;
-    if ((st = resident_pics(c, fn, pn, n + 1, W, H, uv8, pb, hb != nullptr, uv16)))
+    const bool hbd = hb != nullptr, uv8 = uv && !hbd, uv16 = uv && hbd;
+    if ((st = resident_pics(c, fn, pn, n + 1, W, H, uv8, pb, hbd, uv16)))
         return st;
     HIP_TRY(hipSetDevice(c->device));
     // the sub-pel scratch holds the records (its results go to the filter's scratch)
     const size_t rec_bytes = sizeof(svtme_ref_record) * (size_t)n * sbs;
     TfScratch S;
-    if ((st = ensure_buf(&c->d_tfsp, &c->tfsp_cap, rec_bytes)) || (st = tf_scratch(c, n, sbs, false, uv != nullptr, &S, hb != nullptr)))
+    if ((st = ensure_buf(&c->d_tfsp, &c->tfsp_cap, rec_bytes)) || (st = tf_scratch(c, n, sbs, false, uv != nullptr, &S, hbd)))
         return st;
     svtme_ref_record *d_rec = (svtme_ref_record *)c->d_tfsp;
     // the TF-ME jobs: one batch, job k's records (R = 1) at d_rec + k x SBs, the array k_tfsp reads
@@ -463,8 +452,8 @@ static svtme_status tf_window_impl(const char *fn, const TfChroma *uv, const TfH
         return st;
     // the result picture (a new number: a buffer of the pool)
     PicBuf *po;
-    if ((st = alloc_pic(c, out_pn, W, H, &po, uv8, hb != nullptr, uv16)) || (uv8 && (st = alloc_chroma(c, *po))) ||
-        (hb && (st = alloc_hbd(c, *po))) || (uv16 && (st = alloc_hbd_chroma(c, *po))))
+    if ((st = alloc_pic(c, out_pn, W, H, &po, uv8, hbd, uv16)) || (uv8 && (st = alloc_chroma(c, *po))) ||
+        (hbd && (st = alloc_hbd(c, *po))) || (uv16 && (st = alloc_hbd_chroma(c, *po))))
         return st;
     Lane &L = c->lanes[0];
     DevPlane ref[SVTME_MAX_BATCH_JOBS];
@@ -473,39 +462,21 @@ static svtme_status tf_window_impl(const char *fn, const TfChroma *uv, const TfH
     if ((st = join_upload(c, *po, 0)) || (st = after_readers(c, *po, L.s)))
         return st;
     HIP_TRY(svtme_launch_tfsp(&pb[0]->pyr.lv[0], ref, n, W, H, sp_ctl, d_rec, S.sub, L.s));
-    if (uv16) {
-        DevPlane ref16[SVTME_MAX_BATCH_JOBS];
-        for (uint32_t k = 0; k < n; k++) ref16[k] = pb[k + 1]->hbd;
-        TffhcArgs U{};
-        tffhc_fill(U, pb, n, W, H, f_ctl, uv, S);
-        U.dst[0] = po->hchroma[0], U.dst[1] = po->hchroma[1];
-        HIP_TRY(svtme_launch_tffh_pic_yuv(&pb[0]->hbd, ref16, n, W, H, f_ctl, S.sub, (uint16_t *)S.tile, S.wgt, S.e32,
-                                          &po->hbd, &po->pyr.lv[0], &U, L.s));
-        // the 16-bit planes beyond their true sizes and their margins, from their own interiors
-        if ((st = build_hbd(po, (const uint16_t *)po->hbd.base, (uint32_t)po->hbd.stride / 2, src_width, src_height, L.s)))
+    TfLumaArgs Y{};
+    TfChromaArgs U{};
+    tf_stage_fill(Y, U, pb, n, W, H, f_ctl, uv, hbd, S);
+    Y.dst = tf_luma(po, hbd);
+    if (hbd)
+        Y.dst8 = po->pyr.lv[0];
+    for (int p = 0; uv && p < 2; p++) U.dst[p] = tf_chroma(po, p, hbd);
+    HIP_TRY(svtme_launch_tf_stage(&Y, uv ? &U : nullptr, hbd, 1, L.s));
+    // the 16-bit planes beyond their true sizes and their margins, from their own interiors
+    if (hbd && (st = build_hbd(po, (const uint16_t *)po->hbd.base, (uint32_t)po->hbd.stride / 2, src_width, src_height, L.s)))
+        return st;
+    for (int p = 0; uv16 && p < 2; p++)
+        if ((st = build_hbd_chroma(po, p, (const uint16_t *)po->hchroma[p].base, (uint32_t)po->hchroma[p].stride / 2,
+                                   (src_width + 1) >> 1, (src_height + 1) >> 1, L.s)))
             return st;
-        for (int p = 0; p < 2; p++)
-            if ((st = build_hbd_chroma(po, p, (const uint16_t *)po->hchroma[p].base, (uint32_t)po->hchroma[p].stride / 2,
-                                       (src_width + 1) >> 1, (src_height + 1) >> 1, L.s)))
-                return st;
-    } else if (uv) {
-        // both predictions before either normalisation: in place the chroma stage reads the centre's luma
-        TffcArgs U{};
-        tffc_fill(U, pb, n, W, H, f_ctl, uv, S);
-        U.dst[0] = po->chroma[0], U.dst[1] = po->chroma[1];
-        HIP_TRY(svtme_launch_tff_pic_yuv(&pb[0]->pyr.lv[0], ref, n, W, H, f_ctl, S.sub, S.tile, S.wgt, S.e32,
-                                         &po->pyr.lv[0], &U, L.s));
-    } else if (hb) {
-        DevPlane ref16[SVTME_MAX_BATCH_JOBS];
-        for (uint32_t k = 0; k < n; k++) ref16[k] = pb[k + 1]->hbd;
-        HIP_TRY(svtme_launch_tffh_pic(&pb[0]->hbd, ref16, n, W, H, f_ctl, S.sub, (uint16_t *)S.tile, S.wgt, S.e32,
-                                      &po->hbd, &po->pyr.lv[0], L.s));
-        // the 16-bit plane beyond the true size and its margins, from its own interior
-        if ((st = build_hbd(po, (const uint16_t *)po->hbd.base, (uint32_t)po->hbd.stride / 2, src_width, src_height, L.s)))
-            return st;
-    } else
-        HIP_TRY(svtme_launch_tff_pic(&pb[0]->pyr.lv[0], ref, n, W, H, f_ctl, S.sub, S.tile, S.wgt, S.e32,
-                                     &po->pyr.lv[0], L.s));
     // the sub-8 re-pad and the margins from the plane's own interior, then levels 1 and 2
     if ((st = build_pyramid(c, po, po->pyr.lv[0].base, (uint32_t)po->pyr.lv[0].stride, src_width, src_height, 0, L.s)))
         return st;
@@ -648,15 +619,13 @@ static svtme_status tf_ld_check(const char *fn, const svtme_ctx *c, uint64_t cen
 static void tfld_sources(TfldArgs &A, PicBuf *const *pb, uint32_t n, uint32_t W, uint32_t H,
                          const svtme_tf_ld_controls *ctl) {
     const bool hbd = ctl->bit_depth == 10;
-    auto luma      = [hbd](const PicBuf *p) -> const DevPlane & { return hbd ? p->hbd : p->pyr.lv[0]; };
-    auto chroma    = [hbd](const PicBuf *p, int pl) -> const DevPlane & { return hbd ? p->hchroma[pl] : p->chroma[pl]; };
-    A.cen_y        = luma(pb[0]).base;
-    A.y_stride     = luma(pb[0]).stride;
-    for (uint32_t k = 0; k < SVTME_MAX_BATCH_JOBS; k++) A.ref_y[k] = luma(pb[k < n ? k + 1 : 1]).base;
+    A.cen_y        = tf_luma(pb[0], hbd).base;
+    A.y_stride     = tf_luma(pb[0], hbd).stride;
+    for (uint32_t k = 0; k < SVTME_MAX_BATCH_JOBS; k++) A.ref_y[k] = tf_luma(pb[k < n ? k + 1 : 1], hbd).base;
     for (int p = 0; ctl->chroma && p < 2; p++) {
-        A.cen_c[p] = chroma(pb[0], p).base;
-        A.c_stride = chroma(pb[0], p).stride;
-        for (uint32_t k = 0; k < SVTME_MAX_BATCH_JOBS; k++) A.ref_c[p][k] = chroma(pb[k < n ? k + 1 : 1], p).base;
+        A.cen_c[p] = tf_chroma(pb[0], p, hbd).base;
+        A.c_stride = tf_chroma(pb[0], p, hbd).stride;
+        for (uint32_t k = 0; k < SVTME_MAX_BATCH_JOBS; k++) A.ref_c[p][k] = tf_chroma(pb[k < n ? k + 1 : 1], p, hbd).base;
     }
     for (int p = 0; p < 3; p++) A.decay[p] = ctl->tf_decay_factor_fp16[p];
     A.ss        = ctl->sub_sampling_shift;
